@@ -25,6 +25,10 @@ Per-GPU work is fixed as N grows (weak scaling). --scope engine_only: pre-resolv
 device pipeline, one step = one 8192-row micro-batch (the device-pipeline number).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|heuristic]
+                       [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times K steps and prints the result line; --dump-outputs adds the
+last timed step's decoded answers as DIR/<name>.npy (dump_serving_outputs), --full whatever is
+measured beyond the headline figure (nothing at present).
 For N > 1 run under torchrun (the driver does), or this script launches torchrun itself.
 """
 from __future__ import annotations
@@ -111,7 +115,17 @@ def parse():
                     help="fraud configs: the 1h amount sum - sliding (exact, from the tx ring: default) or compat "
                          "(the reference's INCRBY-with-TTL running sum, redis_store.go:136-138; quirk Q8)")
     ap.add_argument("--json-out", default="")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="serving scope, fraud configs: after the timed steps write what the last timed step "
+                         "answered to DIR/<name>.npy (dump_serving_outputs: a fixed sample of its responses, "
+                         "decoded; float32 / float64, the same rows on every run with the same arguments)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the benchmark measures beyond its headline figure. A plain run sets up, "
+                         "warms up, times --steps steps and prints the result line; every other scope, config "
+                         "and size already has an option of its own, so today --full adds nothing")
     a = ap.parse_args()
+    if a.dump_outputs and (a.scope not in ("auto", "serving") or a.config in ("cfg4", "cfg5", "heuristic")):
+        ap.error("--dump-outputs: the serving scope of a fraud model config (cfg1 / cfg2 / cfg3)")
     if a.numerics == "auto":  # the ONNX models' f32 contract everywhere (cfg4 / cfg5: split MFMA)
         a.numerics = "fp32"
     if a.scope == "auto":  # cfg4 / cfg5: the account-RPC serving path, owner-routed over every rank
@@ -716,6 +730,57 @@ def _hot_by_thread(samples, names) -> dict:
     return {k: c.most_common(12) for k, c in hot.items()}
 
 
+DUMP_REQUESTS = 16  # --dump-outputs: responses of the last timed step that are kept and decoded
+
+
+def dump_sample(steps: int, per_step: int) -> dict:
+    """--dump-outputs: {request index: None} of the DUMP_REQUESTS requests of the last timed step
+    whose response bytes the ingress threads keep (a seeded choice, the same on every run)."""
+    pick = np.random.default_rng(20).choice(per_step, min(DUMP_REQUESTS, per_step), replace=False)
+    return {(steps - 1) * per_step + int(k): None for k in sorted(pick)}
+
+
+def dump_serving_outputs(path: str, kept: dict, n_payloads: int, accounts) -> dict:
+    """Decode the kept ScoreBatchResponse bytes of the last timed step (what a ScoreBatch caller
+    receives) into arrays, one row per transaction, requests in index order:
+
+      score, action, rule_score, ml_score   float32 [rows]
+      reasons                               float32 [rows, len(REASON_CODES)]: 1 where the code is set
+      features                              float64 [rows, 26]: the FeatureVector, in field-number order
+
+    response_time_ms (wall clock) is left out. The rows are those whose account occurs once in the
+    whole request stream (``accounts``: per distinct request, the account index of every row):
+    such an account gets one event per pass over the stream, so its state when the row is scored
+    is the same however the ingress threads interleave. An account that several requests in
+    flight share sees their events in arrival order, which differs from run to run."""
+    from igaming_platform_amd.config import REASON_BIT
+    from igaming_platform_amd.proto import risk_v1 as P
+    _, inv, cnt = np.unique(np.concatenate(accounts), return_inverse=True, return_counts=True)
+    once = (cnt[inv] == 1).reshape(len(accounts), -1)
+    fields = [f.name for f in sorted(P.FeatureVector.DESCRIPTOR.fields, key=lambda f: f.number)]
+    head, reasons, feats = [], [], []
+    for i in sorted(kept):
+        res = P.ScoreBatchResponse.FromString(kept[i]).results
+        for r in np.nonzero(once[i % n_payloads])[0].tolist():
+            x = res[r]
+            head.append((x.score, x.action, x.rule_score, x.ml_score))
+            bits = [0.0] * len(REASON_BIT)
+            for code in x.reason_codes:
+                bits[REASON_BIT[code]] = 1.0
+            reasons.append(bits)
+            feats.append([float(getattr(x.features, f)) for f in fields])
+    head = np.asarray(head, np.float64).reshape(-1, 4)
+    out = {"score": head[:, 0].astype(np.float32), "action": head[:, 1].astype(np.float32),
+           "rule_score": head[:, 2].astype(np.float32), "ml_score": head[:, 3].astype(np.float32),
+           "reasons": np.asarray(reasons, np.float32).reshape(-1, len(REASON_BIT)),
+           "features": np.asarray(feats, np.float64).reshape(-1, len(fields))}
+    assert sum(v.nbytes for v in out.values()) <= 64 << 20
+    os.makedirs(path, exist_ok=True)
+    for name, v in out.items():
+        np.save(os.path.join(path, name + ".npy"), v)
+    return {"requests": sorted(kept), "rows": int(len(head)), "dir": path}
+
+
 def serving_bench(a) -> None:
     """The serving objects end to end, every rank ingesting (bench.py --gpus N runs
     the serving path, not a hand-built scorer). Per rank:
@@ -833,7 +898,7 @@ def serving_bench(a) -> None:
     lock = threading.Lock()
     timings = type(core).last_timings
 
-    def run(n_req: int, t_base: int, record: bool):
+    def run(n_req: int, t_base: int, record: bool, keep=None):
         counter = {"i": 0}
 
         def worker():
@@ -853,6 +918,8 @@ def serving_bench(a) -> None:
                     with lock:
                         lat.append(dt)
                         stage_rows.append(tm[:6])
+                    if keep is not None and i in keep:  # --dump-outputs: this response is decoded later
+                        keep[i] = out
         th = [threading.Thread(target=worker) for _ in range(a.threads)]
         [t.start() for t in th]
         [t.join() for t in th]
@@ -883,8 +950,9 @@ def serving_bench(a) -> None:
         if os.environ.get("IGP_BENCH_SAMPLE") == "1":  # + the hottest functions per thread name
             from igaming_platform_amd.native import native as _nat
             _nat().sampler_start(4000, 1 << 21)
+    kept = dump_sample(a.steps, per_step) if a.dump_outputs and rank == 0 else None
     t0 = time.perf_counter()
-    run(a.steps * per_step, NOW0, True)
+    run(a.steps * per_step, NOW0, True, kept)
     sync()
     barrier()
     elapsed = time.perf_counter() - t0
@@ -961,6 +1029,8 @@ def serving_bench(a) -> None:
         xd = getattr(getattr(getattr(node, "local", None), "scorer", None), "xdriver", None)
         if xd is not None:
             out["exchange_waits_us_rank0"] = {k: round(float(v), 1) for k, v in xd.stats().items()}
+    if kept is not None:
+        out["dumped_outputs"] = dump_serving_outputs(a.dump_outputs, kept, len(payloads), spread["accounts"])
     if rank == 0:
         line = json.dumps(out)
         print(line, flush=True)

@@ -94,6 +94,7 @@ def spread_payloads(n_accounts: int, n_payloads: int, batch: int, seed: int, zip
     if stats is not None:  # how much of the population the stream touches
         stats["distinct_accounts"] = int(len(np.unique(np.concatenate(seen))))
         stats["transactions"] = n_payloads * batch
+        stats["accounts"] = seen  # per request: the account index of every transaction
     return out
 
 
