@@ -499,6 +499,61 @@ PYBIND11_MODULE(_hipk, m) {
     check("gru");
   });
   m.def("gru_ws_clusters", [](int n_rows) { return gru_ws_clusters(n_rows); });
+  m.def("lstm", [](py::dict d, uintptr_t s) {
+    LstmArgs a{};
+    a.n_layers = geti(d, "n_layers");
+    if (a.n_layers < 1 || a.n_layers > 2) throw std::runtime_error("lstm: 1 or 2 layers");
+    a.split = geti(d, "split");
+    for (int l = 0; l < a.n_layers; ++l) {
+      const std::string p = "l" + std::to_string(l) + "_";
+      a.layer[l].W = ptr<const uint16_t*>(d, (p + "W").c_str());
+      a.layer[l].R = ptr<const uint16_t*>(d, (p + "R").c_str());
+      a.layer[l].bias = ptr<const float*>(d, (p + "bias").c_str());
+      a.layer[l].kx_pad = geti(d, (p + "kx_pad").c_str());
+      a.layer[l].W_lo = ptr<const uint16_t*>(d, (p + "Wlo").c_str());
+      a.layer[l].R_lo = ptr<const uint16_t*>(d, (p + "Rlo").c_str());
+      if (!a.layer[l].W || !a.layer[l].R || !a.layer[l].bias) throw std::runtime_error("lstm: missing layer weights");
+      if (a.split && (!a.layer[l].W_lo || !a.layer[l].R_lo))
+        throw std::runtime_error("lstm: split mode needs residual weights");
+    }
+    a.H = geti(d, "H");
+    a.T = geti(d, "T");
+    a.I = geti(d, "I");
+    a.mode = geti(d, "mode");
+    a.X = ptr<const float*>(d, "X");
+    a.x_rows = geti(d, "x_rows");
+    a.ev = ptr<const uint16_t*>(d, "ev");
+    a.rt = ptr<const AcctRT*>(d, "rt");
+    a.slots = ptr<const int32_t*>(d, "slots");
+    a.ev_ring = geti(d, "ev_ring");
+    a.m_ptr = ptr<const int32_t*>(d, "m_ptr");
+    a.n_rows = geti(d, "n_rows");
+    a.yh = ptr<float*>(d, "yh");
+    a.head_w = ptr<const float*>(d, "head_w");
+    a.head_b = d.contains("head_b") ? d["head_b"].cast<float>() : 0.f;
+    a.head_act = geti(d, "head_act");
+    a.out = ptr<float*>(d, "out");
+    a.tile_rows = geti(d, "tile_rows");
+    a.reverse = geti(d, "reverse", 0);
+    if (a.tile_rows != 0 && a.tile_rows != 16 && a.tile_rows != 32) throw std::runtime_error("lstm: tile_rows 16|32");
+    if (a.H != 64 && a.H != 128 && a.H != 256) throw std::runtime_error("lstm: H must be 64, 128 or 256");
+    if (a.layer[0].kx_pad != 32 && a.layer[0].kx_pad != 64) throw std::runtime_error("lstm: input dim must pad to 32 or 64");
+    if (a.n_layers == 2 && a.layer[1].kx_pad != a.H) throw std::runtime_error("lstm: layer 2 input must be H");
+    if (a.T < 1) throw std::runtime_error("lstm: T must be positive");
+    if (a.I < 8 || a.I % 8 != 0 || a.I > a.layer[0].kx_pad) throw std::runtime_error("lstm: I must be a multiple of 8 <= kx_pad");
+    if (a.mode != 0 && a.mode != 1) throw std::runtime_error("lstm: mode 0 (dense) | 1 (event ring)");
+    if (a.mode == 1 && (!a.ev || !a.rt || !a.slots || a.ev_ring < a.T)) throw std::runtime_error("lstm: event-ring input");
+    if (a.mode == 0 && (!a.X || a.x_rows < a.n_rows)) throw std::runtime_error("lstm: dense input");
+    if (a.head_w && !a.out) throw std::runtime_error("lstm: head needs out");
+    if (!a.head_w && !a.yh) throw std::runtime_error("lstm: nothing to write (no head, no yh)");
+    if (recording()) throw std::runtime_error("lstm: not recordable; use graphs");
+    launch_lstm(a, stream_of(s));
+    check("lstm");
+  });
+  m.def("lstm_tile_rows", [](int H, int kx_pad, int split, int requested) {
+    if ((H != 64 && H != 128 && H != 256) || (kx_pad != 32 && kx_pad != 64)) throw std::runtime_error("lstm_tile_rows: shape");
+    return lstm_tile_rows(H, kx_pad, split, requested);
+  });
 
   m.def("mlp_chain", [](py::dict d, uintptr_t s) {
     MlpChainArgs a{};

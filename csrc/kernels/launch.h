@@ -307,6 +307,42 @@ bool gru_wsx_eligible(const GruArgs& a);
 void launch_gru_wsx(const GruArgs& a, hipStream_t st);
 int gru_wsx_clusters(int n_rows);
 
+// ---- K4 LSTM (1-2 stacked ONNX LSTM layers, gates i, o, f, c, zero initial states) + optional
+// N=1 head: the batch-parallel design of the GRU kernel (lstm.hip). Weights fragment-packed as
+// above with N = 4H rows (gate-major: the gate g tile of hidden tile ht is column tile g*H/16 + ht).
+struct LstmLayerArgs {
+  const uint16_t* W;        // packed bf16, N = 4H rows, K = kx_pad
+  const uint16_t* R;        // packed bf16, N = 4H rows, K = H
+  const float* bias;        // [8H]: Wb i,o,f,c | Rb i,o,f,c
+  int32_t kx_pad;
+  const uint16_t* W_lo;     // split mode: bf16 residuals, same fragment order
+  const uint16_t* R_lo;
+};
+struct LstmArgs {
+  LstmLayerArgs layer[2];
+  int32_t n_layers, H, T, I;
+  int32_t mode;             // 0 dense X f32 [T][x_rows][I]; 1 per-account event ring (bf16 [C][ring][I])
+  const float* X;
+  int32_t x_rows;
+  const uint16_t* ev;
+  const AcctRT* rt;
+  const int32_t* slots;     // [rows] (-1 -> empty history)
+  int32_t ev_ring;
+  const int32_t* m_ptr;     // live row count on device (nullable)
+  int32_t n_rows;
+  float* yh;                // [rows][H] last layer's final hidden state (nullable)
+  const float* head_w;      // [H] (nullable): out[r] = act(h . w + b)
+  float head_b;
+  int32_t head_act;         // 0 none, 2 sigmoid
+  float* out;               // [rows]
+  int32_t tile_rows;        // 0 / 16 | 32 rows per workgroup (32 only where the LDS allows)
+  int32_t split;            // 1: f32-faithful bf16 hi/lo pairs, three MFMAs per product
+  int32_t reverse;          // 1: ONNX direction=reverse: time steps read last to first
+};
+void launch_lstm(const LstmArgs& a, hipStream_t st);
+// rows per workgroup launch_lstm uses (16, or 32 when requested and the activation tiles fit the LDS)
+int lstm_tile_rows(int H, int kx_pad, int split, int requested);
+
 // ---- K9 LTV / churn / segment
 struct LtvArgs {
   const float* pf;          // [B][25] player features (golden.ltv.PLAYER_COLUMNS), or the table when slots != null

@@ -201,6 +201,80 @@ void gru(const onnx::Node& n, const Tensor& X, const Tensor& W, const Tensor& R,
   }
 }
 
+// ONNX LSTM (gates i, o, f, c), default activations sigmoid / tanh / tanh, optional peepholes
+// P [D][3H] (i, o, f), directions and layouts as for the GRU above; Y_c / initial_c are shaped
+// like Y_h / initial_h. Products accumulate in double, the gates are float, as in gru().
+void lstm(const onnx::Node& n, const Tensor& X, const Tensor& W, const Tensor& R, const Tensor* Bp,
+          const Tensor* h0, const Tensor* c0, const Tensor* Pp, Tensor& Y, Tensor& Yh, Tensor& Yc) {
+  const int64_t H = n.geti("hidden_size", R.dims.back());
+  const int64_t layout = n.geti("layout", 0);
+  if (layout != 0 && layout != 1) throw std::runtime_error("LSTM: layout must be 0 or 1");
+  std::string dir = n.gets("direction", "forward");
+  if (dir != "forward" && dir != "reverse" && dir != "bidirectional") throw std::runtime_error("LSTM: direction");
+  const int64_t D = dir == "bidirectional" ? 2 : 1;
+  if (auto a = n.attr("activations")) {
+    static const char* const def[3] = {"Sigmoid", "Tanh", "Tanh"};
+    if (int64_t(a->strings.size()) != 3 * D) throw std::runtime_error("LSTM: activations must name 3 functions per direction");
+    for (size_t k = 0; k < a->strings.size(); ++k)
+      if (a->strings[k] != def[k % 3])
+        throw std::runtime_error("LSTM: activations other than Sigmoid / Tanh / Tanh are not supported (" + a->strings[k] + ")");
+  }
+  if (n.attr("activation_alpha") || n.attr("activation_beta"))
+    throw std::runtime_error("LSTM: activation_alpha / activation_beta are not supported");
+  if (n.attr("clip")) throw std::runtime_error("LSTM: clip is not supported");
+  if (n.geti("input_forget", 0) != 0) throw std::runtime_error("LSTM: input_forget = 1 is not supported");
+  if (X.dims.size() != 3) throw std::runtime_error("LSTM: X must be rank 3");
+  const int64_t S = layout ? X.dims[1] : X.dims[0], Bn = layout ? X.dims[0] : X.dims[1], I = X.dims[2];
+  if (W.dims.size() != 3 || W.dims[0] != D || W.dims[1] != 4 * H || W.dims[2] != I) throw std::runtime_error("LSTM: W shape");
+  if (R.dims.size() != 3 || R.dims[0] != D || R.dims[1] != 4 * H || R.dims[2] != H) throw std::runtime_error("LSTM: R shape");
+  if (Bp && Bp->numel() != D * 8 * H) throw std::runtime_error("LSTM: B shape");
+  if (Pp && Pp->numel() != D * 3 * H) throw std::runtime_error("LSTM: P shape");
+  if (h0 && h0->numel() != D * Bn * H) throw std::runtime_error("LSTM: initial_h shape");
+  if (c0 && c0->numel() != D * Bn * H) throw std::runtime_error("LSTM: initial_c shape");
+  Y = layout ? make({Bn, S, D, H}) : make({S, D, Bn, H});
+  Yh = layout ? make({Bn, D, H}) : make({D, Bn, H});
+  Yc = Yh;
+  auto xo = [&](int64_t t, int64_t b) { return (layout ? b * S + t : t * Bn + b) * I; };
+  auto yo = [&](int64_t t, int64_t d, int64_t b) { return (layout ? (b * S + t) * D + d : (t * D + d) * Bn + b) * H; };
+  auto ho = [&](int64_t d, int64_t b) { return (layout ? b * D + d : d * Bn + b) * H; };
+  std::vector<double> g(4 * H);
+  for (int64_t d = 0; d < D; ++d) {
+    const bool rev = dir == "reverse" || (D == 2 && d == 1);
+    const float* w = &W.f[d * 4 * H * I];
+    const float* r = &R.f[d * 4 * H * H];
+    std::vector<float> bias(8 * H, 0.f), peep(3 * H, 0.f);
+    if (Bp) std::copy(Bp->f.begin() + d * 8 * H, Bp->f.begin() + (d + 1) * 8 * H, bias.begin());
+    if (Pp) std::copy(Pp->f.begin() + d * 3 * H, Pp->f.begin() + (d + 1) * 3 * H, peep.begin());
+    for (int64_t b = 0; b < Bn; ++b) {
+      std::vector<float> h(H, 0.f), c(H, 0.f);
+      if (h0) std::copy(h0->f.begin() + ho(d, b), h0->f.begin() + ho(d, b) + H, h.begin());
+      if (c0) std::copy(c0->f.begin() + ho(d, b), c0->f.begin() + ho(d, b) + H, c.begin());
+      for (int64_t st = 0; st < S; ++st) {
+        const int64_t t = rev ? S - 1 - st : st;
+        const float* x = &X.f[xo(t, b)];
+        for (int64_t j = 0; j < 4 * H; ++j) {  // rows of W / R: i | o | f | c
+          double ax = 0, ah = 0;
+          for (int64_t k = 0; k < I; ++k) ax += double(w[j * I + k]) * x[k];
+          for (int64_t k = 0; k < H; ++k) ah += double(r[j * H + k]) * h[k];
+          g[j] = ax + ah + bias[j] + bias[4 * H + j];
+        }
+        for (int64_t j = 0; j < H; ++j) {
+          const float ig = sigmoid(float(g[j] + double(peep[j]) * c[j]));
+          const float fg = sigmoid(float(g[2 * H + j] + double(peep[2 * H + j]) * c[j]));
+          const float ct = std::tanh(float(g[3 * H + j]));
+          const float cn = fg * c[j] + ig * ct;
+          const float og = sigmoid(float(g[H + j] + double(peep[H + j]) * cn));
+          c[j] = cn;
+          h[j] = og * std::tanh(cn);
+        }
+        std::copy(h.begin(), h.end(), Y.f.begin() + yo(t, d, b));
+      }
+      std::copy(h.begin(), h.end(), Yh.f.begin() + ho(d, b));
+      std::copy(c.begin(), c.end(), Yc.f.begin() + ho(d, b));
+    }
+  }
+}
+
 // ---- ai.onnx.ml linear models and preprocessing (sklearn-style pipelines: Scaler ->
 // LinearClassifier -> ZipMap; Normalizer; LinearRegressor). Semantics follow the ai.onnx.ml
 // operator definitions; ORT itself is not available offline, so exact ORT parity is unpinned
@@ -563,6 +637,17 @@ std::map<std::string, Tensor> Executor::run(const std::map<std::string, Tensor>&
       if (opt(n, 4)) throw std::runtime_error("GRU: sequence_lens is not supported");
       if (!n.outputs.empty() && !n.outputs[0].empty()) vals[n.outputs[0]] = Y;
       if (n.outputs.size() > 1 && !n.outputs[1].empty()) vals[n.outputs[1]] = Yh;
+      continue;
+    } else if (op == "LSTM") {
+      // inputs: X, W, R, B, sequence_lens, initial_h, initial_c, P; outputs: Y, Y_h, Y_c
+      if (n.inputs.size() < 3) throw std::runtime_error("LSTM: needs X, W and R");
+      if (opt(n, 4)) throw std::runtime_error("LSTM: sequence_lens is not supported");
+      Tensor Y, Yh, Yc;
+      lstm(n, get(n.inputs[0]), get(n.inputs[1]), get(n.inputs[2]), opt(n, 3), opt(n, 5), opt(n, 6), opt(n, 7),
+           Y, Yh, Yc);
+      if (!n.outputs.empty() && !n.outputs[0].empty()) vals[n.outputs[0]] = Y;
+      if (n.outputs.size() > 1 && !n.outputs[1].empty()) vals[n.outputs[1]] = Yh;
+      if (n.outputs.size() > 2 && !n.outputs[2].empty()) vals[n.outputs[2]] = Yc;
       continue;
     } else {
       throw std::runtime_error("executor: unsupported op " + op + " (node " + n.name + ")");

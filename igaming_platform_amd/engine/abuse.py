@@ -98,10 +98,10 @@ class AbuseGpu:
         # batch then reads the store after every scoring batch issued before it
         self.state_clock = None
         steps = plan.steps
-        from .runner import GruModel
+        from .runner import sequence_model
         # fp32 plans (the ONNX f32 contract, default): the f32-faithful split GRU; bf16 plans: bf16 MFMA
         bmax_ = max([int(b) for b in buckets] or [bmax])
-        self.gm = GruModel(steps, self.device, getattr(plan, "precision", "fp32") != "bf16", bmax_)
+        self.gm = sequence_model(steps, self.device, getattr(plan, "precision", "fp32") != "bf16", bmax_)
         if not self.gm.has_head:
             raise ValueError("abuse model must end in an N=1 head (probability)")
         self.gp = self.gm.packs[0]  # (the weight-stationary path and its fallback live on this pack)

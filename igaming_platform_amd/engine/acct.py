@@ -121,7 +121,7 @@ class AbuseNativeDevice:
                  max_batch: int = 0, priority: int = 0, cluster_kernel: bool = True):
         import torch
         from ..ops import kernels as K
-        from .runner import GruModel
+        from .runner import sequence_model
         self.be, self.depth = backend, int(depth)
         store, sc = backend.store, backend.scorer
         dev = store.device
@@ -133,7 +133,7 @@ class AbuseNativeDevice:
             raise ValueError("abuse bucket larger than the store's batch capacity")
         self.gm = None
         if plan is not None:
-            self.gm = GruModel(plan.steps, dev, getattr(plan, "precision", "fp32") != "bf16", B)
+            self.gm = sequence_model(plan.steps, dev, getattr(plan, "precision", "fp32") != "bf16", B)
             if not self.gm.has_head:
                 raise ValueError("abuse model must end in an N=1 head (probability)")
             # the bf16 cluster kernel (gru_ws.hip) needs the whole chip co-resident, which a

@@ -41,6 +41,7 @@ import numpy as np
 import torch
 
 from ..layouts import REQREC
+from ..models.plan import has_sequence
 from ..native import hipk
 from ..ops import kernels as K
 from ..parallel.exchange import FEAT_BYTES, RES_BYTES, build_chunks, gather_results, result_width
@@ -380,7 +381,7 @@ class DpGpuScorer(GpuScorer):
         # when the results go through the node-shared region (no result all-to-all inside them).
         # A two-kernel hipGraphLaunch costs ~20 us of host time and one thread issues every step
         # (profiles/NOTES.md round 5). GRU plans keep graphs (as the single-GPU pipeline).
-        self.stage_ops = self.captured and not any(s.kind == "gru" for s in (self.plan.steps if self.plan else []))
+        self.stage_ops = self.captured and not has_sequence(self.plan.steps if self.plan else [])
         if self.stage_ops:
             with torch.cuda.device(dev):
                 for (C, slot) in self.xgraphs:
@@ -416,7 +417,7 @@ class DpGpuScorer(GpuScorer):
         dev = self.device
         self.direct = False
         self.captured = False
-        self.stage_ops = not any(s.kind == "gru" for s in (self.plan.steps if self.plan else []))
+        self.stage_ops = not has_sequence(self.plan.steps if self.plan else [])
         m = hipk()
         d = m.XchgDriver(self.cstream.cuda_stream, self.stream.cuda_stream, self.mstream.cuda_stream,
                          self.xstream.cuda_stream, self.ystream.cuda_stream, self.depth, self.world, None, None)

@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from ..models.plan import Plan, step_consumers, step_inputs
+from ..models.plan import Plan, has_sequence, step_consumers, step_inputs
 from ..ops import kernels as K
 
 
@@ -44,13 +44,17 @@ class GruModel:
     Input: dense X f32 [T, rows, I] (the ONNX layout-0 order; layout-1 plans are fed the same,
     see :meth:`DeviceModel.run`) or the store's event rings for ``slots``."""
 
+    kind = "gru"     # the plan step kind, weight pack and launch of the cell (LstmModel overrides)
+    pack = K.GruPack
+    launch = staticmethod(K.gru)
+
     def __init__(self, steps, device, split: bool, bmax: int):
         n = 0
-        while n < len(steps) and steps[n].kind == "gru":
+        while n < len(steps) and steps[n].kind == self.kind:
             n += 1
         head = steps[n] if n < len(steps) and steps[n].kind == "dense" and steps[n].n == 1 else None
         if n == 0 or n + (head is not None) != len(steps):
-            raise ValueError("sequence model must be GRU layers followed by at most an N=1 head")
+            raise ValueError(f"sequence model must be {self.kind.upper()} layers followed by at most an N=1 head")
         g = steps[0]
         self.H = g.hidden
         self.seq = g.seq
@@ -58,13 +62,13 @@ class GruModel:
         self.head = head
         if g.bidirectional:
             if n != 1:
-                raise ValueError("bidirectional GRU: one layer")
-            self.packs = [K.GruPack([g.direction(0)], None, device, split=split),
-                          K.GruPack([g.direction(1)], None, device, split=split, reverse=True)]
+                raise ValueError(f"bidirectional {self.kind.upper()}: one layer")
+            self.packs = [self.pack([g.direction(0)], None, device, split=split),
+                          self.pack([g.direction(1)], None, device, split=split, reverse=True)]
             self.yh = [torch.zeros((bmax, self.H), dtype=torch.float32, device=device) for _ in range(2)]
             self.cat = torch.zeros((bmax, 2 * self.H), dtype=torch.float32, device=device)
         else:
-            self.packs = [K.GruPack(steps[:n], head, device, split=split, reverse=g.reverse)]
+            self.packs = [self.pack(steps[:n], head, device, split=split, reverse=g.reverse)]
 
     @property
     def has_head(self) -> bool:
@@ -81,17 +85,33 @@ class GruModel:
         if not self.bidirectional:
             gp = self.packs[0]
             if self.head is not None:
-                K.gru(gp, n_rows, T, out=out, X=X, store=store, slots=slots, m_ptr=m_ptr)
+                self.launch(gp, n_rows, T, out=out, X=X, store=store, slots=slots, m_ptr=m_ptr)
             else:
-                K.gru(gp, n_rows, T, yh=out, X=X, store=store, slots=slots, m_ptr=m_ptr)
+                self.launch(gp, n_rows, T, yh=out, X=X, store=store, slots=slots, m_ptr=m_ptr)
             return
         for gp, yh in zip(self.packs, self.yh):
-            K.gru(gp, n_rows, T, yh=yh, X=X, store=store, slots=slots, m_ptr=m_ptr)
+            self.launch(gp, n_rows, T, yh=yh, X=X, store=store, slots=slots, m_ptr=m_ptr)
         dst = self.cat if self.head is not None else out
         torch.cat([self.yh[0][:n_rows], self.yh[1][:n_rows]], dim=1, out=dst[:n_rows])
         if self.head is not None:
             h = self.head
             K.dense(self.cat, h.w, h.b, out, n_rows, 1, 2 * self.H, act=h.act, m_ptr=m_ptr)
+
+
+class LstmModel(GruModel):
+    """The LSTM part of a plan on the device (K4 LSTM, csrc/kernels/lstm.hip): the same launch
+    structure and interface as :class:`GruModel`, on ``LstmPack`` / ``lstm``."""
+
+    kind = "lstm"
+    pack = K.LstmPack
+    launch = staticmethod(K.lstm)
+
+
+def sequence_model(steps, device, split: bool, bmax: int):
+    """The device runner of a sequence plan's recurrent layers (+ head): GRU or LSTM."""
+    if steps and steps[0].kind == "lstm":
+        return LstmModel(steps, device, split, bmax)
+    return GruModel(steps, device, split, bmax)
 
 
 class DeviceModel:
@@ -110,7 +130,7 @@ class DeviceModel:
             cons = self.consumers[i]
             feeds_mma = (not last) and bool(cons) and all(steps[j].kind in ("dense", "head", "join") for j in cons)
             # bf16 plans hand bf16 activations to the MFMA layers reading them; fp32 plans stay f32
-            dt = (torch.bfloat16 if (s.kind in ("dense", "gru", "join") and feeds_mma and plan.precision == "bf16")
+            dt = (torch.bfloat16 if (s.kind in ("dense", "gru", "lstm", "join") and feeds_mma and plan.precision == "bf16")
                   else torch.float32)
             self.step_out.append(torch.zeros((B, s.out_width), dtype=dt, device=self.device))
             if s.kind == "tree":
@@ -124,11 +144,12 @@ class DeviceModel:
         # counter per 64-row tile (the kernel returns them to zero)
         self.tile_cnt = torch.zeros(-(-B // 64), dtype=torch.int32, device=self.device)
         # sequence models: the GRU layers (+ an N=1 head) run as ONE fused K4 launch
-        # (a bidirectional layer: two launches + the head, GruModel)
-        self.gru: Optional[GruModel] = None
+        # (a bidirectional layer: two launches + the head, GruModel / LstmModel; the attribute
+        # keeps its name for either cell)
+        self.gru = None
         self.gru_steps = 0
-        if any(s.kind == "gru" for s in steps):
-            self.gru = GruModel(steps, self.device, plan.precision != "bf16", B)
+        if has_sequence(steps):
+            self.gru = sequence_model(steps, self.device, plan.precision != "bf16", B)
             self.gru_steps = len(steps)
             self.seq_len = steps[0].seq
         self.out = self.step_out[-1] if self.step_out else None

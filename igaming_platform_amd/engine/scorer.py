@@ -48,7 +48,7 @@ import torch
 from ..config import Config
 from ..layouts import (BATCHHDR, FEATREC, MODEL_HEURISTIC, MODEL_NONE, MODEL_OUTPUT, REQREC, score_cfg,
                        unpack_results)
-from ..models.plan import Plan
+from ..models.plan import Plan, has_sequence
 from ..ops import kernels as K
 from .runner import DeviceModel
 
@@ -227,8 +227,9 @@ class GpuScorer:
         sb.res = torch.zeros((B, 2), dtype=torch.int32, device=dev)
         sb.model = None
         if self.plan is not None:
-            if any(s.kind == "gru" for s in self.plan.steps):
-                raise ValueError("fraud scoring models take a feature vector; GRU models run in the abuse scorer")
+            if has_sequence(self.plan.steps):
+                raise ValueError("fraud scoring models take a feature vector; sequence models (GRU / LSTM) run in "
+                                 "the abuse scorer")
             sb.model = DeviceModel(self.plan, dev, self.buckets)
         return sb
 
@@ -361,7 +362,7 @@ class GpuScorer:
             # direct launch (csrc/kernels/oplist.h): the stages' kernels issued as plain launches
             # instead of graph replays (a graph launch costs ~7 us of queue time on MI355X)
             self.direct = (os.environ.get("IGP_DIRECT_LAUNCH", "1") == "1"
-                           and not any(s.kind == "gru" for s in (self.plan.steps if self.plan else [])))
+                           and not has_sequence(self.plan.steps if self.plan else []))
             if self.direct:
                 with torch.cuda.device(self.device):
                     for b in self.buckets:

@@ -13,6 +13,8 @@ steps:
 * ``DenseStep``  Gemm / MatMul(+Add) with a following Relu/Sigmoid/Tanh fused into the
                  epilogue -> K3 ``gemm`` (MFMA) or ``gemv`` (N == 1).
 * ``GRUStep``    ONNX GRU (forward / reverse / bidirectional, layout 0 / 1) -> K4 (cfg 5).
+* ``LSTMStep``   ONNX LSTM (same directions / layouts, default activations, no peepholes) -> K4
+                 ``lstm`` (csrc/kernels/lstm.hip).
 * ``JoinStep``   Add / Concat of two branches (residual blocks, wide & deep) -> ``join``.
 * ai.onnx.ml ``LinearClassifier`` / ``LinearRegressor`` (post NONE / LOGISTIC; a two-class
   SOFTMAX as sigmoid(s1 - s0)) -> a dense layer, so an sklearn pipeline
@@ -176,6 +178,49 @@ class GRUStep:
 
 
 @dataclass
+class LSTMStep:
+    """One ONNX LSTM layer (gate order i, o, f, c; sigmoid / tanh / tanh; zero initial states)."""
+    hidden: int
+    in_dim: int
+    w_np: np.ndarray     # [4H, I]
+    r_np: np.ndarray     # [4H, H]
+    b_np: np.ndarray     # [8H]: Wb i,o,f,c | Rb i,o,f,c
+    seq: int = 0
+    kind: str = "lstm"
+    src: Optional[int] = None
+    reverse: bool = False
+    layout: int = 0
+    bidirectional: bool = False
+    w_rev_np: Optional[np.ndarray] = None
+    r_rev_np: Optional[np.ndarray] = None
+    b_rev_np: Optional[np.ndarray] = None
+
+    @property
+    def out_width(self) -> int:
+        return self.hidden * (2 if self.bidirectional else 1)
+
+    def direction(self, d: int) -> "LSTMStep":
+        """One direction of a bidirectional layer as a unidirectional step (d = 1: reverse)."""
+        if d == 0:
+            return LSTMStep(self.hidden, self.in_dim, self.w_np, self.r_np, self.b_np, seq=self.seq,
+                            layout=self.layout)
+        return LSTMStep(self.hidden, self.in_dim, self.w_rev_np, self.r_rev_np, self.b_rev_np, seq=self.seq,
+                        reverse=True, layout=self.layout)
+
+
+SEQUENCE_KINDS = ("gru", "lstm")   # recurrent steps: the plan is then a sequence model
+
+
+def is_sequence_step(s) -> bool:
+    return s.kind in SEQUENCE_KINDS
+
+
+def has_sequence(steps) -> bool:
+    """Whether the steps form a sequence model (GRU / LSTM layers: [T, rows, I] input, K4)."""
+    return any(is_sequence_step(s) for s in steps or ())
+
+
+@dataclass
 class Plan:
     family: str
     in_width: int
@@ -211,7 +256,7 @@ class Plan:
             elif s.kind == "join":
                 parts.append(f"{s.op}(#{s.a},#{s.b})")
             else:
-                parts.append(f"gru(I={s.in_dim},H={s.hidden})")
+                parts.append(f"{s.kind}(I={s.in_dim},H={s.hidden})")
         return " -> ".join(parts)
 
 
@@ -262,7 +307,7 @@ class _Val:
     cpu_col: int = 0          # ... and in the CPU executor's output of the same value
     narrowed: bool = False    # a binary classifier lowered to its positive column only
     label: bool = False       # a classifier's label output (not lowered)
-    gru_y: bool = False       # a GRU's per-step outputs (only another GRU layer reads them)
+    gru_y: bool = False       # a GRU's / LSTM's per-step outputs Y (only another such layer reads them)
     bidir_pending: bool = False  # a layout-0 bidirectional Y_h still in [D, N, H] order
 
 
@@ -363,7 +408,8 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
         if v.narrowed:
             raise PlanError(f"{what}: reads a binary classifier's scores (lowered to the positive column)")
         if v.gru_y:
-            raise PlanError(f"{what}: a GRU's per-step outputs are lowered only into another GRU layer")
+            cell = steps[v.step].kind.upper()
+            raise PlanError(f"{what}: a {cell}'s per-step outputs are lowered only into another {cell} layer")
         return v
 
     def plain(name, what) -> _Val:
@@ -553,7 +599,8 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
                 raise PlanError(f"{op}: value {x!r} is not computed by a lowered node")
             v = vals[x]
             if op == "Reshape" and v.bidir_pending:
-                raise PlanError("bidirectional GRU: Y_h [2, N, H] must be transposed to [N, 2, H] before reshaping")
+                raise PlanError(f"bidirectional {steps[v.step].kind.upper()}: Y_h [2, N, H] must be transposed to "
+                                "[N, 2, H] before reshaping")
             if op == "Cast" and int(a.get("to", 1)) != 1:
                 raise PlanError("Cast to a non-float type is not lowered")
             vals[n["outputs"][0]] = v
@@ -562,7 +609,7 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
             # only the direction <-> batch swap of a layout-0 GRU's Y_h ([D, N, H] -> [N, D, H])
             v = vals.get(x)
             perm = [int(p) for p in a.get("perm", [])]
-            if (v is None or v.step < 0 or steps[v.step].kind != "gru" or steps[v.step].layout != 0
+            if (v is None or v.step < 0 or not is_sequence_step(steps[v.step]) or steps[v.step].layout != 0
                     or perm != [1, 0, 2]):
                 raise PlanError("Transpose is lowered only as perm [1, 0, 2] on a GRU's final states")
             vals[n["outputs"][0]] = replace(v, bidir_pending=False)
@@ -579,6 +626,8 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
                 raise PlanError("GRU: sequence_lens is not lowered")
             if len(ins) > 5 and ins[5]:
                 raise PlanError("GRU: initial_h is not lowered (the device starts every sequence at zero)")
+            if any(s.kind == "lstm" for s in steps):
+                raise PlanError("GRU: GRU and LSTM layers mixed in one chain are not lowered")
             prev = [s for s in steps if s.kind == "gru"]
             if prev and (direction == "bidirectional" or prev[0].bidirectional
                          or prev[0].reverse != (direction == "reverse") or prev[0].layout != layout):
@@ -601,6 +650,63 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
             y, yh = n["outputs"][0], (n["outputs"][1] if len(n["outputs"]) > 1 else "")
             if D == 2 and y and uses.get(y, 0) > 0:
                 raise PlanError("bidirectional GRU: only the final states (Y_h) are lowered")
+            if y:
+                vals[y] = _Val(idx, H * D, gru_y=True)
+            if yh:
+                vals[yh] = _Val(idx, H * D, bidir_pending=D == 2 and layout == 0)
+            continue
+        if op == "LSTM":
+            v = vals.get(x)
+            if v is None or v.scale is not None or (v.step >= 0 and not v.gru_y):
+                raise PlanError("LSTM: the input must be the model input or the previous layer's Y")
+            direction = a.get("direction", "forward")
+            layout = int(a.get("layout", 0))
+            if direction not in ("forward", "reverse", "bidirectional") or layout not in (0, 1):
+                raise PlanError(f"LSTM: direction {direction!r} / layout {layout} is not lowered")
+            D = 2 if direction == "bidirectional" else 1
+            if len(ins) > 4 and ins[4]:
+                raise PlanError("LSTM: sequence_lens is not lowered")
+            if len(ins) > 5 and ins[5]:
+                raise PlanError("LSTM: initial_h is not lowered (the device starts every sequence at zero)")
+            if len(ins) > 6 and ins[6]:
+                raise PlanError("LSTM: initial_c is not lowered (the device starts every cell state at zero)")
+            if len(ins) > 7 and ins[7]:
+                raise PlanError("LSTM: peepholes (P) are not lowered")
+            acts = [str(s) for s in a.get("activations", [])]
+            if acts and acts != ["Sigmoid", "Tanh", "Tanh"] * D:
+                raise PlanError(f"LSTM: activations {acts} are not lowered (Sigmoid / Tanh / Tanh only)")
+            if "activation_alpha" in a or "activation_beta" in a:
+                raise PlanError("LSTM: activations with alpha / beta are not lowered")
+            if "clip" in a:
+                raise PlanError("LSTM: clip is not lowered")
+            if int(a.get("input_forget", 0)):
+                raise PlanError("LSTM: input_forget = 1 is not lowered")
+            if any(s.kind == "gru" for s in steps):
+                raise PlanError("LSTM: GRU and LSTM layers mixed in one chain are not lowered")
+            prev = [s for s in steps if s.kind == "lstm"]
+            if prev and (D == 2 or prev[0].bidirectional
+                         or prev[0].reverse != (direction == "reverse") or prev[0].layout != layout):
+                raise PlanError("LSTM: stacked layers must share direction and layout (bidirectional: one layer)")
+            Wa = np.asarray(const(ins[1]), np.float32)
+            Ra = np.asarray(const(ins[2]), np.float32)
+            H = int(a.get("hidden_size", Ra.shape[-1]))
+            Ba = (np.asarray(const(ins[3]), np.float32).reshape(D, 8 * H)
+                  if len(ins) > 3 and ins[3] else np.zeros((D, 8 * H), np.float32))
+            if Wa.shape[0] != D or Ra.shape[0] != D:
+                raise PlanError("LSTM: weight direction count does not match the direction attribute")
+            if Wa.shape[1] != 4 * H or Ra.shape[1:] != (4 * H, H):
+                raise PlanError("LSTM: W / R must be [D, 4H, I] / [D, 4H, H]")
+            outs_n = list(n["outputs"]) + ["", "", ""]
+            y, yh, yc = outs_n[0], outs_n[1], outs_n[2]
+            if yc and (uses.get(yc, 0) > 0 or yc in outs):
+                raise PlanError("LSTM: the final cell state Y_c is consumed, which is not lowered")
+            seq = dims[1] if layout == 1 else dims[0]
+            idx = emit(LSTMStep(hidden=H, in_dim=int(Wa.shape[2]), w_np=Wa[0], r_np=Ra[0], b_np=Ba[0],
+                                seq=int(seq) if seq > 0 else 0, reverse=direction == "reverse", layout=layout,
+                                bidirectional=D == 2, w_rev_np=Wa[1] if D == 2 else None,
+                                r_rev_np=Ra[1] if D == 2 else None, b_rev_np=Ba[1] if D == 2 else None), v.step)
+            if D == 2 and y and uses.get(y, 0) > 0:
+                raise PlanError("bidirectional LSTM: only the final states (Y_h) are lowered")
             if y:
                 vals[y] = _Val(idx, H * D, gru_y=True)
             if yh:
@@ -667,14 +773,13 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
         fv = plain(output_name, "output")
     if not steps or fv.step != len(steps) - 1:
         raise PlanError("the output must be computed by the last lowered step")
-    if any(s.kind == "gru" for s in steps) and any(s.kind == "join" or s.src != i - 1
-                                                   for i, s in enumerate(steps)):
-        raise PlanError("sequence models are lowered as chains (GRU layers + head) only")
+    if has_sequence(steps) and any(s.kind == "join" or s.src != i - 1 for i, s in enumerate(steps)):
+        raise PlanError("sequence models are lowered as chains (GRU / LSTM layers + head) only")
     fam = model.metadata.get("family", "")
     if not fam:
         kinds = [s.kind for s in steps]
         fam = ("gbdt" if kinds == ["tree"] else "stacked" if kinds and kinds[0] == "tree"
-               else "gru" if "gru" in kinds else "mlp")
+               else "gru" if "gru" in kinds else "lstm" if "lstm" in kinds else "mlp")
     plan = Plan(family=fam, in_width=in_width, steps=steps, out_width=fv.width, ml_col=fv.ml_col,
                 metadata=dict(model.metadata), input_name=input_name, output_name=output_name,
                 seq_input=seq_input, cpu_col=fv.cpu_col)

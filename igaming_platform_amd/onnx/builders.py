@@ -179,6 +179,63 @@ def gru(seq: int = 100, in_dim: int = 16, hidden: int = 256, seed: int = 5, laye
                            "direction": direction, "layout": str(layout)})
 
 
+def _lstm_weights(rng, in_dim: int, hidden: int):
+    s = 1.0 / np.sqrt(hidden)
+    w = rng.uniform(-s, s, (1, 4 * hidden, in_dim)).astype(np.float32)
+    r = rng.uniform(-s, s, (1, 4 * hidden, hidden)).astype(np.float32)
+    b = rng.uniform(-s, s, (1, 8 * hidden)).astype(np.float32)
+    return w, r, b
+
+
+def lstm(seq: int = 100, in_dim: int = 16, hidden: int = 256, seed: int = 11, layers: int = 2,
+         head: bool = True, direction: str = "forward", layout: int = 0):
+    """LSTM sequence classifier (ONNX gate order i, o, f, c), built like :func:`gru`: ``direction``
+    forward / reverse / bidirectional (one layer), ``layout`` 0 ([seq, N, in]) or 1 ([N, seq, in])."""
+    rng = np.random.default_rng(seed)
+    D = 2 if direction == "bidirectional" else 1
+    if D == 2 and layers != 1:
+        raise ValueError("bidirectional: one layer")
+
+    def weights(i):
+        ws = [_lstm_weights(rng, i, hidden) for _ in range(D)]
+        return tuple(np.concatenate([w[k] for w in ws], 0) for k in range(3))
+    w1, r1, b1 = weights(in_dim)
+    wh = (rng.standard_normal((D * hidden, 1)) * np.sqrt(1.0 / (D * hidden))).astype(np.float32)
+    bh = np.array([0.0], np.float32)
+    attrs = dict(hidden_size=hidden)
+    if direction != "forward":
+        attrs["direction"] = direction
+    if layout:
+        attrs["layout"] = int(layout)
+    nodes = [node("LSTM", ["input", "W1", "R1", "B1"], ["Y1", "Yh1"], **attrs)]
+    # Y: layout 0 [seq, D, N, H] -> squeeze axis 1; layout 1 [N, seq, D, H] -> squeeze axis 2
+    inits = [tensor("W1", w1), tensor("R1", r1), tensor("B1", b1),
+             tensor("ax1", np.array([2 if layout else 1], np.int64)),
+             tensor("shp", np.array([-1, D * hidden], np.int64))]
+    last_h = "Yh1"
+    if layers == 2:
+        w2, r2, b2 = weights(hidden)
+        nodes += [node("Squeeze", ["Y1", "ax1"], ["X2"]),
+                  node("LSTM", ["X2", "W2", "R2", "B2"], ["Y2", "Yh2"], **attrs)]
+        inits += [tensor("W2", w2), tensor("R2", r2), tensor("B2", b2)]
+        last_h = "Yh2"
+    if D == 2 and not layout:  # Y_h [2, N, H] -> [N, 2, H] -> [N, 2H]
+        nodes.append(node("Transpose", [last_h], ["hT"], perm=[1, 0, 2]))
+        last_h = "hT"
+    if head:
+        nodes += [node("Reshape", [last_h, "shp"], ["h"]), node("Gemm", ["h", "Wh", "Bh"], ["logit"]),
+                  node("Sigmoid", ["logit"], ["output"])]
+        inits += [tensor("Wh", wh), tensor("Bh", bh)]
+        out_vi = value_info("output", S.FLOAT, ["N", 1])
+    else:
+        nodes.append(node("Reshape", [last_h, "shp"], ["output"]))
+        out_vi = value_info("output", S.FLOAT, ["N", D * hidden])
+    x_dims = ["N", seq, in_dim] if layout else [seq, "N", in_dim]
+    return model(nodes, [value_info("input", S.FLOAT, x_dims)], [out_vi], inits, name="abuse_lstm",
+                 metadata={"family": "lstm", "layers": str(layers), "hidden": str(hidden), "seq": str(seq),
+                           "direction": direction, "layout": str(layout)})
+
+
 def _scaler(rng, n_features: int):
     """sklearn StandardScaler as ai.onnx.ml Scaler: (x - mean) * (1 / std)."""
     mean = rng.uniform(-0.5, 0.5, n_features).astype(np.float32)
@@ -287,6 +344,7 @@ def residual_mlp(n_features: int = 32, width: int = 128, blocks: int = 2, seed: 
 
 
 BUILDERS = {"logistic": logistic, "gbdt": gbdt, "stacked": stacked, "ltv_mlp": ltv_mlp, "gru": gru,
+            "lstm": lstm,
             "sklearn_linear": sklearn_linear, "linear_regressor": linear_regressor,
             "mlp_classifier": mlp_classifier, "wide_deep": wide_deep, "residual_mlp": residual_mlp}
 

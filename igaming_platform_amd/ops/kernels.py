@@ -672,6 +672,111 @@ def gru(gp: GruPack, n_rows: int, T: int, out: Optional[torch.Tensor] = None, yh
     _mod().gru(d, _stream())
 
 
+# --------------------------------------------------------------------------- K4 (LSTM)
+class LstmPack:
+    """Device weights of a 1-2 layer LSTM chain (+ optional N=1 head) for csrc/kernels/lstm.hip.
+    ``layers``: models.plan.LSTMStep (w_np [4H, I], r_np [4H, H], b_np [8H], ONNX gate order)."""
+
+    def __init__(self, layers, head=None, device="cuda", split: bool = False, reverse: bool = False):
+        """``split`` / ``reverse``: as for :class:`GruPack`."""
+        import numpy as np
+        if not 1 <= len(layers) <= 2:
+            raise ValueError("lstm: 1 or 2 stacked layers are lowered")
+        H = layers[0].hidden
+        if H not in (64, 128, 256):
+            raise ValueError("lstm: hidden size must be 64, 128 or 256")
+        if layers[0].in_dim < 8 or layers[0].in_dim % 8 or layers[0].in_dim > 64:
+            raise ValueError("lstm: input dim must be a multiple of 8, <= 64")
+        if len(layers) == 2 and (layers[1].hidden != H or layers[1].in_dim != H):
+            raise ValueError("lstm: layer 2 must be H -> H")
+        self.H, self.I, self.n_layers = H, layers[0].in_dim, len(layers)
+        self.reverse = bool(reverse)
+        dev = as_device(device)
+        self.split = bool(split)
+        self.x3_rows = 16  # rows per workgroup of the split kernel (32: see AbuseGpu overlap)
+        self.layers = []
+
+        def residual(w):
+            w = np.ascontiguousarray(w, np.float32)
+            return w - torch.from_numpy(w).to(torch.bfloat16).float().numpy()
+        for i, l in enumerate(layers):
+            kx = H if i == 1 else (32 if l.in_dim <= 32 else 64)
+            if l.w_np.shape != (4 * H, l.in_dim) or l.r_np.shape != (4 * H, H) or l.b_np.shape != (8 * H,):
+                raise ValueError("lstm: W / R / B must be [4H, I] / [4H, H] / [8H]")
+            self.layers.append(dict(W=pack_fragments(l.w_np, kx).to(dev), R=pack_fragments(l.r_np, H).to(dev),
+                                    Wlo=pack_fragments(residual(l.w_np), kx).to(dev) if self.split else None,
+                                    Rlo=pack_fragments(residual(l.r_np), H).to(dev) if self.split else None,
+                                    bias=torch.from_numpy(np.ascontiguousarray(l.b_np, np.float32)).to(dev),
+                                    kx_pad=kx))
+        self.head_w = self.head_b = None
+        self.head_act = 0
+        if head is not None:
+            if head.n != 1 or head.k != H or head.act not in ("none", "sigmoid"):
+                raise ValueError("lstm: head must be dense H -> 1 with none/sigmoid")
+            self.head_w = torch.from_numpy(np.ascontiguousarray(head.w_np[0], np.float32)).to(dev)
+            self.head_b = float(head.b_np[0]) if head.b_np is not None else 0.0
+            self.head_act = ACT[head.act]
+        self.device = dev
+        # no weight-stationary cluster variants: the abuse runners' handling of these reads False
+        self.ws_ok = self.wsx_ok = False
+        self.ws_err = None
+
+    def ws_failed(self) -> bool:
+        return False
+
+    def disable_ws(self, keep_wsx: bool = False) -> None:
+        """Nothing to disable (batch-parallel kernel only); kept for the runners' GruPack interface."""
+
+
+def lstm(lp: LstmPack, n_rows: int, T: int, out: Optional[torch.Tensor] = None, yh: Optional[torch.Tensor] = None,
+         X: Optional[torch.Tensor] = None, store=None, slots: Optional[torch.Tensor] = None,
+         m_ptr: Optional[torch.Tensor] = None, tile_rows: int = 0) -> None:
+    """K4 (LSTM). Input either dense ``X`` f32 [T, rows, I] or the store's event rings for ``slots``;
+    writes ``out`` [rows] (a pack with a head) or ``yh`` [rows, H] (the last layer's final h)."""
+    dev = lp.device
+    if T < 1:
+        raise ValueError("lstm: T must be positive")
+    d = dict(n_layers=lp.n_layers, H=lp.H, T=int(T), I=lp.I, n_rows=int(n_rows),
+             m_ptr=_opt(m_ptr, "m_ptr", dtype=torch.int32, device=dev), tile_rows=int(tile_rows))
+    if lp.split:
+        d["split"] = 1
+        if not tile_rows:
+            d["tile_rows"] = int(lp.x3_rows)
+    if lp.reverse:
+        d["reverse"] = 1
+    for i, l in enumerate(lp.layers):
+        kx = l["kx_pad"]
+        d[f"l{i}_W"] = _need(l["W"], "W", torch.bfloat16, 4 * lp.H * kx, dev)
+        d[f"l{i}_R"] = _need(l["R"], "R", torch.bfloat16, 4 * lp.H * lp.H, dev)
+        if lp.split:
+            d[f"l{i}_Wlo"] = _need(l["Wlo"], "Wlo", torch.bfloat16, 4 * lp.H * kx, dev)
+            d[f"l{i}_Rlo"] = _need(l["Rlo"], "Rlo", torch.bfloat16, 4 * lp.H * lp.H, dev)
+        d[f"l{i}_bias"] = _need(l["bias"], "bias", torch.float32, 8 * lp.H, dev)
+        d[f"l{i}_kx_pad"] = kx
+    if X is not None:
+        if X.dim() != 3 or X.shape[0] < T or X.shape[1] < n_rows or X.shape[2] != lp.I:
+            raise ValueError(f"lstm: X must be [T>={T}, rows>={n_rows}, {lp.I}]")
+        d.update(mode=0, X=_need(X, "X", torch.float32, device=dev), x_rows=int(X.shape[1]))
+    else:
+        if store is None or slots is None or store.ev is None:
+            raise ValueError("lstm: need X or (store with event rings, slots)")
+        if store.ev.shape[2] != lp.I or store.ev.shape[1] < T:
+            raise ValueError("lstm: event ring width / length does not match the model")
+        d.update(mode=1, ev=_need(store.ev, "ev", torch.int16, device=dev),
+                 rt=_need(store.rt, "rt", torch.int32, device=dev),
+                 slots=_need(slots, "slots", torch.int32, n_rows, dev), ev_ring=int(store.ev.shape[1]))
+    if yh is not None:
+        d["yh"] = _need(yh, "yh", torch.float32, n_rows * lp.H, dev)
+    if lp.head_w is not None:
+        if out is None:
+            raise ValueError("lstm: a model with a head needs out")
+        d.update(head_w=_need(lp.head_w, "head_w", torch.float32, lp.H, dev), head_b=lp.head_b,
+                 head_act=lp.head_act, out=_need(out, "out", torch.float32, n_rows, dev))
+    elif yh is None:
+        raise ValueError("lstm: nothing to write (no head, no yh)")
+    _mod().lstm(d, _stream())
+
+
 # --------------------------------------------------------------------------- K3 fused MLP chain
 class MlpChainPack:
     """Device weights of a dense chain for the fused kernel (csrc/kernels/mlp_fused.hip):
