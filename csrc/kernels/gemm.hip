@@ -57,7 +57,8 @@ __global__ void __launch_bounds__(256) gemm_kernel(GemmArgs a) {
       if (row < M) {
         if (a.x_bf16) {
           const uint16_t* src = reinterpret_cast<const uint16_t*>(a.X) + (size_t)row * a.ldx + k;
-          if (k + 8 <= K) {
+          // 16-byte load only from 16-byte-aligned rows (ldx % 8 == 0), as the f32 branch below
+          if (k + 8 <= K && ((a.ldx & 7) == 0)) {
             v = *reinterpret_cast<const uint4*>(src);
           } else {
             uint16_t t[8];
@@ -388,10 +389,12 @@ __global__ void __launch_bounds__(256) mlp_head_kernel(HeadArgs a, int w_lds) {
     }
     const float b1 = sb1[n];
     const float w2 = sw2[n];
+    // a padded column (n >= N1) has an all-zero W1 row: 0 x Inf = NaN there must not reach the row sum
+    const bool live_n = n < a.N1;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) part[i][q] += act_fn(acc[i][q] + b1, a.act1) * w2;
+      for (int q = 0; q < 4; ++q) part[i][q] += live_n ? act_fn(acc[i][q] + b1, a.act1) * w2 : 0.f;
   }
   // reduce over the 16 lanes that share rows (lane & 15 = column), then over the 4 waves
 #pragma unroll
@@ -528,10 +531,12 @@ __global__ void __launch_bounds__(256) mlp_head_f32_kernel(HeadArgs a, int w_lds
     }
     const float b1 = sb1[n];
     const float w2 = sw2[n];
+    // a padded column (n >= N1) has an all-zero W1 row: 0 x Inf = NaN there must not reach the row sum
+    const bool live_n = n < a.N1;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) part[i][q] += act_fn(acc[i][q] + b1, a.act1) * w2;
+      for (int q = 0; q < 4; ++q) part[i][q] += live_n ? act_fn(acc[i][q] + b1, a.act1) * w2 : 0.f;
   }
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -674,6 +679,8 @@ __global__ void __launch_bounds__(256) mlp_head_f32_fast_kernel(HeadArgs a) {
     for (int s = 0; s < KS; ++s) bv[s] = *reinterpret_cast<const float4*>(&sW[n * LR + s * 16 + 4 * (lane >> 4)]);
     const float b1 = sb1[n];
     const float w2 = sw2[n];
+    // a padded column (n >= N1) has an all-zero W1 row: 0 x Inf = NaN there must not reach the row sum
+    const bool live_n = n < a.N1;
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
@@ -682,8 +689,8 @@ __global__ void __launch_bounds__(256) mlp_head_f32_fast_kernel(HeadArgs a) {
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      part[0][q] += act_fn(acc0[q] + b1, ACT) * w2;
-      part[1][q] += act_fn(acc1[q] + b1, ACT) * w2;
+      part[0][q] += live_n ? act_fn(acc0[q] + b1, ACT) * w2 : 0.f;
+      part[1][q] += live_n ? act_fn(acc1[q] + b1, ACT) * w2 : 0.f;
     }
   }
 #pragma unroll
