@@ -11,6 +11,10 @@
 
 #define IGP_DEVICE_OPS_ABI 4
 
+// bits of IgpDeviceOps::submit's want_features argument
+#define IGP_SUBMIT_WANT_FEATURES 1
+#define IGP_SUBMIT_NO_UPDATE 2
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -28,6 +32,10 @@ typedef struct IgpDeviceOps {
   char* (*rows)(void* ctx, int32_t slot);
   // launch the slot's batch: n live rows (exchange: ignored, counts ride in the chunk
   // headers), batch sequence number, scoring clock. Returns 0, or -1 with a message in err.
+  // want_features is a set of IGP_SUBMIT_* bits: bit 0 asks for the FeatRec rows; bit 1 is the
+  // caller's proof that no account has more than K1_SEG_MAX rows in this batch (mult_sketch.h),
+  // so a device whose K1 applies those accounts itself may skip the multi-event update launch.
+  // Devices without such a launch (CPU shards) and the exchange pipeline ignore bit 1.
   int32_t (*submit)(void* ctx, int32_t slot, int32_t n, int32_t seq, int64_t now, int32_t want_features, char* err,
                     int32_t errlen);
   // block until the slot's batch completed: 0 ok, 1 timeout (timeout_us >= 0), -1 error

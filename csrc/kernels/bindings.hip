@@ -172,6 +172,7 @@ PYBIND11_MODULE(_hipk, m) {
     a.dbuf = ptr<int32_t*>(d, "dbuf");
     a.dcap = geti(d, "dcap");
     a.dmax = geti(d, "dmax");
+    a.own_short = geti(d, "own_short", 0);
     a.x_stride = geti(d, "x_stride");
     a.ring_size = geti(d, "ring_size");
     a.n_rows = geti(d, "n_rows");

@@ -1,8 +1,9 @@
 // Native micro-batch driver for the three-stream scoring pipeline (engine/scorer.py).
 //
 // Per batch the scorer replays three captured hipGraphs on three streams linked by events:
-//   copy   : wait model_ev[slot] (slot buffers free), wait state_ev[batch-2] (its K1 cleared this
-//            batch's dedup region) -> graph(copy)  -> record copy_ev[slot]
+//   copy   : wait model_ev[slot] (slot buffers free), wait the post-state event of batch
+//            seq - DEDUP_AHEAD (its K1 cleared this batch's dedup region) -> graph(copy)
+//            -> record copy_ev[slot]
 //   state  : wait copy_ev[slot]  -> graph(state) -> record state_ev[slot]
 //   model  : wait state_ev[slot] -> graph(model) -> record model_ev[slot]
 // Issued from Python this costs ~110 us of host time per batch (stream contexts, torch event
@@ -28,6 +29,7 @@
 #include <vector>
 
 #include "../include/device_ops.h"
+#include "../include/mult_sketch.h"
 #include "../include/records.h"
 #include "launch.h"
 #include "oplist.h"
@@ -38,6 +40,8 @@ namespace py = pybind11;
 
 namespace igp {
 namespace {
+
+static_assert(IGP_K1_SEG_MAX == K1_SEG_MAX, "the host's bound and K1 agree on the accounts K1 owns");
 
 void hip_ok(hipError_t e, const char* what) {
   if (e != hipSuccess) throw std::runtime_error(std::string("PipeDriver ") + what + ": " + hipGetErrorString(e));
@@ -83,7 +87,7 @@ class PipeDriver {
     ev_.resize(3 * depth);
     for (size_t i = 0; i < ev_.size(); ++i)
       hip_ok(hipEventCreateWithFlags(&ev_[i], i % 3 == 2 ? hipEventDisableTiming : dev_flags), "event create");
-    if (depth > DEDUP_AHEAD)  // batch q's dedup region was cleared by batch q - DEDUP_AHEAD's update
+    if (depth > DEDUP_AHEAD)  // batch q's dedup region was cleared by batch q - DEDUP_AHEAD's K1
       throw std::runtime_error("PipeDriver: depth exceeds the dedup ring (DEDUP_AHEAD)");
     for (auto& e : pe_) hip_ok(hipEventCreateWithFlags(&e, dev_flags), "event create");
     pe_seq_.fill(-1);
@@ -105,6 +109,14 @@ class PipeDriver {
   // stage-end events bound to the stages' last kernels (oplist.h) instead of recorded markers
   void set_ext_events(bool on) { ext_events_ = on; }
   bool ext_events() const { return ext_events_; }
+
+  // Launch the multi-event update behind every K1, also where the submitter's bound shows that
+  // no account needs it (tests compare the two schedules)
+  void set_always_update(bool on) { always_update_ = on; }
+  bool always_update() const { return always_update_; }
+  // batches whose update launch was skipped / issued since the driver was made
+  int64_t update_skips() const { return update_skips_; }
+  int64_t update_launches() const { return update_launches_; }
 
   // the slot's pinned result rows (ResultRec [bucket]) and FeatRec rows: what the native
   // serving core reads after wait (device_ops)
@@ -150,7 +162,8 @@ class PipeDriver {
         if (bucket < 0) throw std::runtime_error("batch exceeds the largest bucket");
         auto it = d->graphs_.find(key(bucket, slot));
         if (it == d->graphs_.end()) throw std::runtime_error("no graphs for this bucket / slot");
-        d->issue(Cmd{slot, bucket, n, seq, now, 0, wf != 0, it->second});
+        d->issue(Cmd{slot, bucket, n, seq, now, 0, (wf & IGP_SUBMIT_WANT_FEATURES) != 0,
+                     (wf & IGP_SUBMIT_NO_UPDATE) != 0, false, it->second});
       } catch (const std::exception& e) {
         copy_err(err, errlen, e.what());
         return -1;
@@ -202,10 +215,13 @@ class PipeDriver {
   }
   // readers of the feature store order themselves after the last published state stage
   void set_state_clock(std::shared_ptr<StateClock> c) { clock_ = std::move(c); }
-  // direct launch with a split state stage: `s` of set_ops holds K1 only, `su` the update
-  void set_state_update(int bucket, int slot, std::shared_ptr<OpList> su) {
+  // direct launch with a split state stage: `s` of set_ops holds K1 only, `su` the update;
+  // `sk` (nullable): the K1 that owns the short multi-event accounts (AssembleArgs::own_short),
+  // issued instead of `s` + `su` for a batch in which no account has more than K1_SEG_MAX rows
+  void set_state_update(int bucket, int slot, std::shared_ptr<OpList> su, std::shared_ptr<OpList> sk) {
     if (slot < 0 || slot >= depth_) throw std::runtime_error("PipeDriver: bad slot");
     graphs_[key(bucket, slot)].osu = std::move(su);
+    graphs_[key(bucket, slot)].osk = std::move(sk);
   }
 
   // rows: pointer to n packed ReqRec (0: already in the slab); the batch is tracked by its slot
@@ -216,8 +232,12 @@ class PipeDriver {
     if (slot < 0 || slot >= depth_) throw std::runtime_error("PipeDriver: bad slot");
     auto it = graphs_.find(key(bucket, slot));
     if (it == graphs_.end()) throw std::runtime_error("PipeDriver: no graphs for this bucket/slot");
-    const Cmd c{slot, bucket, n, seq, now, rows, with_features, it->second};
+    Cmd c{slot, bucket, n, seq, now, rows, with_features, false, false, it->second};
     py::gil_scoped_release nogil;
+    // the same bound the serving core passes down (device_ops.h IGP_SUBMIT_NO_UPDATE), over the
+    // rows this call copies into the slab; rows already in the slab: no bound, the update runs
+    // (computed in issue(), in the pass that copies them)
+    c.bound_rows = rows && c.g.osu && c.g.osk && !always_update_;
     issue(c);
   }
 
@@ -226,6 +246,7 @@ class PipeDriver {
     hipGraphExec_t c = nullptr, s = nullptr, m = nullptr, mf = nullptr;  // mf: + FeatRec rows to the host
     std::shared_ptr<OpList> oc, os, om, omf;  // direct-launch mode (set_ops)
     std::shared_ptr<OpList> osu;              // split state stage: the update after K1
+    std::shared_ptr<OpList> osk;              // ... or this K1 alone (it owns the short multi-event accounts)
   };
   static void stage(hipGraphExec_t g, const std::shared_ptr<OpList>& ops, hipStream_t st, const char* what) {
     if (ops) ops->run(st);
@@ -244,6 +265,8 @@ class PipeDriver {
     int64_t now;
     uintptr_t rows;
     bool with_features;
+    bool no_update;  // no account has more than K1_SEG_MAX rows in the batch (mult_sketch.h)
+    bool bound_rows = false;  // work no_update out from `rows` while copying them
     Graphs g;
   };
 
@@ -256,7 +279,15 @@ class PipeDriver {
     Range range("igp.submit");
     const auto t0 = clk::now();
     char* slab = slabs_[slot];
-    if (rows) std::memcpy(slab + sizeof(BatchHdr), reinterpret_cast<const void*>(rows), (size_t)n * sizeof(ReqRec));
+    bool no_update = cmd.no_update;
+    if (rows && cmd.bound_rows) {
+      thread_local MultSketch sk;
+      sk.build(reinterpret_cast<const ReqRec*>(rows), (size_t)(n > 0 ? n : 0),
+               reinterpret_cast<ReqRec*>(slab + sizeof(BatchHdr)));
+      no_update = sk.max <= IGP_K1_SEG_MAX;
+    } else if (rows) {
+      std::memcpy(slab + sizeof(BatchHdr), reinterpret_cast<const void*>(rows), (size_t)n * sizeof(ReqRec));
+    }
     const auto t1 = clk::now();
     BatchHdr* h = reinterpret_cast<BatchHdr*>(slab);
     h->n = n;
@@ -275,7 +306,7 @@ class PipeDriver {
     // waited for K1). An event query first: no queue wait when it already finished.
     if (hipEvent_t e = post_event(prev_seq); e && hipEventQuery(e) != hipSuccess)
       hip_ok(hipStreamWaitEvent(cs_, e, 0), "wait slot update");
-    // the state stage of batch seq - DEDUP_AHEAD cleared this batch's dedup region (the post
+    // K1 of batch seq - DEDUP_AHEAD cleared this batch's dedup region (the post
     // events are kept per batch in a ring of DEDUP_RING, so this is exact at any depth <= AHEAD)
     if (hipEvent_t e = post_event(seq - DEDUP_AHEAD); e && hipEventQuery(e) != hipSuccess)
       hip_ok(hipStreamWaitEvent(cs_, e, 0), "wait state-ahead");
@@ -285,16 +316,31 @@ class PipeDriver {
     if (!cb) hip_ok(hipEventRecord(ce, cs_), "record copy");
     hip_ok(hipStreamWaitEvent(ss_, ce, 0), "wait copy");
     const auto t4 = clk::now();
-    const bool sb = stage_rec(g.s, g.os, ss_, se, "state graph");
+    // Split state stage (direct launch) of a batch in which no account has more than K1_SEG_MAX
+    // rows: the K1 that owns the short multi-event accounts runs (`osk`); it applies every event
+    // and clears the dedup region of batch seq + DEDUP_AHEAD, and no update is launched. Any
+    // other batch runs the plain K1 and the update, which then applies every multi-event
+    // account (the hot accounts need the launch anyway). The skipped update's post-state event
+    // then is K1's own: bound to its dispatch here, and the model stream waits on it. (Not the
+    // slot's state event under a second name: that one is re-bound `depth` batches later, and
+    // the copy of batch seq + DEDUP_AHEAD would wait for the later batch.)
+    const bool skip_update = g.osu && g.osk && no_update && !always_update_;
+    hipEvent_t ke = skip_update ? pe : se;  // completes with K1
+    const bool sb = stage_rec(g.s, skip_update ? g.osk : g.os, ss_, ke, "state graph");
     const auto t5 = clk::now();
-    if (!sb) hip_ok(hipEventRecord(se, ss_), "record state");
-    hip_ok(hipStreamWaitEvent(ms_, se, 0), "wait state");
-    // split state stage (direct launch): the model waited for K1 only; the multi-event update
-    // (which also clears the dedup region of batch seq+3) follows on the state stream and its
-    // own event gates that region's reuse
-    const bool pb = g.osu && ext_events_ && g.osu->run_recording(ss_, pe);
-    if (g.osu && !ext_events_) g.osu->run(ss_);
-    if (!pb) hip_ok(hipEventRecord(pe, ss_), "record post");
+    if (!sb) hip_ok(hipEventRecord(ke, ss_), "record state");
+    hip_ok(hipStreamWaitEvent(ms_, ke, 0), "wait state");
+    if (skip_update) {
+      ++update_skips_;
+    } else {
+      // split state stage: the model waited for K1 only; the update of the accounts with more
+      // than K1_SEG_MAX events follows on the state stream and the batch's post-state event,
+      // which gates the reuse of the slot's rows and of the dedup region K1 cleared, is its own
+      const bool pb = g.osu && ext_events_ && g.osu->run_recording(ss_, pe);
+      if (g.osu && !ext_events_) g.osu->run(ss_);
+      if (!pb) hip_ok(hipEventRecord(pe, ss_), "record post");
+      ++update_launches_;
+    }
     if (clock_) clock_->publish(pe);  // K1 + the multi-event update of this batch
     const auto t6 = clk::now();
     const bool mb = stage_rec(with_features ? g.mf : g.m, with_features ? g.omf : g.om, ms_, me, "model graph");
@@ -370,6 +416,8 @@ class PipeDriver {
   std::shared_ptr<StateClock> clock_;
   std::unordered_map<int64_t, Graphs> graphs_;
   bool ext_events_ = true;
+  bool always_update_ = false;
+  int64_t update_skips_ = 0, update_launches_ = 0;  // written by the issuing thread
   // native serving core interface
   std::vector<char*> host_res_, host_feat_;
   std::vector<int> buckets_;
@@ -398,6 +446,10 @@ void register_driver(py::module_& m) {
       .def("set_state_update", &PipeDriver::set_state_update)
       .def("set_ext_events", &PipeDriver::set_ext_events)
       .def_property_readonly("ext_events", &PipeDriver::ext_events)
+      .def("set_always_update", &PipeDriver::set_always_update)
+      .def_property_readonly("always_update", &PipeDriver::always_update)
+      .def_property_readonly("update_skips", &PipeDriver::update_skips)
+      .def_property_readonly("update_launches", &PipeDriver::update_launches)
       .def("submit", &PipeDriver::submit)
       .def("wait", &PipeDriver::wait)
       .def("query", &PipeDriver::query)

@@ -572,7 +572,8 @@ class XchgDriver {
       // launches per batch, the same shape as the single-GPU pipeline
       // the slot's previous batch (q - depth) finished: its buffers are free, and its state
       // stage - with every earlier one, the state stream runs in order - cleared this batch's
-      // dedup region (cleared by batch q - DEDUP_AHEAD, and depth <= DEDUP_AHEAD)
+      // dedup region (cleared by K1 of batch q - DEDUP_AHEAD, and depth <= DEDUP_AHEAD). This
+      // pipeline launches the multi-event update behind every K1.
       if (done_recorded_[slot]) hip_ok(hipStreamWaitEvent(cs_, e_done, 0), "wait done");
       hip_ok(hipGraphLaunch(g.send, cs_), "send+post graph");
       hip_ok(hipEventRecord(e_post, cs_), "record post");

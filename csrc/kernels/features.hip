@@ -23,8 +23,7 @@ __device__ __forceinline__ float k1_hi(int l) {
        : l == 15 ? 86400.f : 1.f;
 }
 
-__device__ void apply_segment_wave(const UpdateArgs& a, const DedupTab& t, int h, int c, int s, AcctRT r,
-                                   int lane);
+__device__ void apply_list_segment(const UpdateArgs& a, const DedupTab& t, int h, int c, int s, AcctRT r, int lane);
 
 // K1 runs one request per 16-lane quarter of a wave (4 requests per wave, 16 per block): the
 // per-request work is either 16-wide (tx ring, HLL registers, model inputs, ext row) or scalar
@@ -32,6 +31,8 @@ __device__ void apply_segment_wave(const UpdateArgs& a, const DedupTab& t, int h
 // whole wave takes a quarter of the VALU issue slots. Reductions / ballots stay inside the
 // quarter (xor shuffles 1..8, ballot bits of the quarter).
 constexpr int K1_QL = 16;  // lanes per request
+static_assert(K1_SEG_MAX <= K1_QL, "a leader holds one row of its account per lane");
+constexpr int K1_SEG_W = 7;  // words per row of a leader's LDS table (odd: rows on different banks)
 
 __device__ __forceinline__ uint32_t qballot(bool p, int qb) { return (uint32_t)(__ballot(p) >> qb) & 0xffffu; }
 
@@ -305,16 +306,54 @@ __device__ __forceinline__ void write_fenc(const AssembleArgs& a, int row, int q
   out[ql] = reinterpret_cast<const uint2*>(fw)[ql];
 }
 
+// The parts of a row's flags and rule pass that its request decides (the rest comes from the
+// account's state, which a leader's rows share: feature_assemble_body).
+__device__ __forceinline__ int k1_row_flags(int ipf, bool blacklisted) {
+  int fl = 0;
+  if (ipf & 1) fl |= FR_VPN;
+  if (ipf & 2) fl |= FR_PROXY;
+  if (ipf & 4) fl |= FR_TOR;
+  if (blacklisted) fl |= FR_BLACKLISTED;
+  return fl;
+}
+struct K1Rules {
+  int score;         // rules 0, 2, 3, 6: decided by the account's state alone
+  uint32_t reasons;
+  bool young;        // rule 1's account side: account_age_days < new_account_days
+  bool rapid;        // rule 5's account side: recent tx, deposits, withdrawals > 80 % of deposits
+};
+__device__ __forceinline__ void k1_row_rules(const ScoreCfg& cfg, const K1Rules& ru, int flags, int64_t amount,
+                                             int tx_type, int32_t& reasons_out, int32_t& score_out) {
+  int score = ru.score;
+  uint32_t reasons = ru.reasons;
+  if (ru.young && amount > cfg.large_deposit_amount) { score += cfg.w_new_account_large_tx; reasons |= 1u << 1; }
+  if (flags & (FR_VPN | FR_PROXY | FR_TOR)) { score += cfg.w_vpn; reasons |= 1u << 4; }
+  if (ru.rapid && tx_type == TX_WITHDRAW) { score += cfg.w_rapid_deposit_withdraw; reasons |= 1u << 5; }
+  if (flags & FR_BLACKLISTED) { score += cfg.w_known_fraudster; reasons |= 1u << 7; }
+  reasons_out = (int32_t)reasons;
+  score_out = score > 100 ? 100 : score;
+}
+// model inputs that a request decides (19-21 ip-intel flags, 26 amount, 27-29 tx type; 22 is never set)
+constexpr uint32_t K1_ROW_INPUTS = (7u << 19) | (15u << 26);
+
 // Loads are organised in two dependency levels (under a full grid each dependent global-load
 // level costs microseconds): level 1 = the request row + batch header + config words; level 2
 // = everything the row addresses (ts ring, amounts, HLL registers, account rows, ext row, dedup
 // probe, blacklist / ip-intel first probe slot), issued branch-free before the first use.
 // Score-then-update: dedup_insert_list_kernel registered the batch first; a request whose
-// account has no other event in the batch applies its event right after its own reads; the
-// accounts with several events are applied after K1 by update_multi_kernel, in row order. (An
-// in-kernel hand-off - the last request of an account to finish its reads applies the
-// account's events - put chains of device-scope atomics and dependent loads at the end of
-// K1: a 20 us tail behind 14 us of work at B=8192.)
+// account has no other event in the batch applies its event right after its own reads. With
+// a.own_short (a batch in which no account has more than K1_SEG_MAX events, so that no update
+// launch follows) an account with 2..K1_SEG_MAX events is owned from start to finish by the quarter of its first
+// row (the leader): the insert left its count, first row and row list, so the leader reads the
+// account's state once, produces every one of its rows' outputs (each scored against the
+// pre-batch state, as their own quarters would) and then applies the events in row order; the
+// quarters of the account's other rows write nothing. No hand-off between waves: an in-kernel
+// hand-off - the last request of an account to finish its reads applies the account's events -
+// put chains of device-scope atomics and dependent loads at the end of K1 (a 20 us tail behind
+// 14 us of work at B=8192). Without own_short every multi-event account is scored row by row and
+// applied after K1 by update_segments_kernel: under Zipf traffic the hot accounts need that launch
+// anyway, and hundreds of leaders in K1 cost more than it saves (96 -> 63 M scores/s measured).
+// K1 also clears the dedup region of batch seq + DEDUP_AHEAD.
 __device__ __forceinline__ void feature_assemble_body(const AssembleArgs& a) {
   // phase trace of every wave: [wave][16] = wall_clock64 marks 0..7, [8] HW_ID, [9] XCC_ID
   const int gw = (int)((blockIdx.x * 256 + threadIdx.x) >> 6);  // launched with 256 threads
@@ -341,6 +380,8 @@ __device__ __forceinline__ void feature_assemble_body(const AssembleArgs& a) {
   __shared__ __attribute__((aligned(16))) float s_xst[16][144];
   __shared__ __attribute__((aligned(16))) uint2 s_fst[16][16];
   __shared__ __attribute__((aligned(16))) uint8_t s_enc[16][128];  // encoded FeatureVector bodies
+  // per quarter: the rows of the short multi-event account it leads (K1_SEG_W words per row)
+  __shared__ int s_seg[16][K1_SEG_MAX][K1_SEG_W];
   const int lc0 = a.hll_lc[threadIdx.x];
   const int lc1 = threadIdx.x == 0 ? a.hll_lc[256] : 0;
   // ---- level 1
@@ -376,6 +417,7 @@ __device__ __forceinline__ void feature_assemble_body(const AssembleArgs& a) {
     inert_row(a, xr, row, ql, ext_w, foreign ? FR_NOT_OWNED : 0);
   }
   int h = -1, s = -1, dcount = 0;
+  int lead_c = 0;  // > 1: this quarter leads an account with that many events in the batch
   K1_MARK(6);
   if (live) {
     s = rq.slot;
@@ -425,7 +467,7 @@ __device__ __forceinline__ void feature_assemble_body(const AssembleArgs& a) {
     for (int u = 0; u < 7; ++u) extv[u] = e[max(0, min(ql + 16 * u, ext_w - 1))];
     // dedup probe (without a dedup region: the batch header, masked below)
     uint32_t dh = 0;
-    const int32_t *pkey, *pfirst, *pcount, *phour;
+    const int32_t *pkey, *pfirst, *pcount, *phour, *plist;
     if (a.dbuf) {  // kernel-uniform
       const DedupTab t = dedup_region(a.dbuf, a.dcap, a.dmax, dedup_ring_region(seq));
       dh = mix32((uint32_t)sc) & (uint32_t)(t.cap - 1);
@@ -433,12 +475,14 @@ __device__ __forceinline__ void feature_assemble_body(const AssembleArgs& a) {
       pfirst = t.first + dh;
       pcount = t.count + dh;
       phour = t.ctr + 1;
+      plist = t.list + (size_t)dh * DEDUP_LIST + ql;  // the account's row list, one entry per lane
     } else {
-      pkey = pfirst = pcount = phour = reinterpret_cast<const int32_t*>(a.hdr);
+      pkey = pfirst = pcount = phour = plist = reinterpret_cast<const int32_t*>(a.hdr);
     }
     int dkey = *pkey, dfirst = *pfirst;
     dcount = *pcount;
     uint32_t hour_word = (uint32_t)*phour;
+    int lrow = *plist;
     if (!a.dbuf) {
       dkey = dfirst = -1;
       dcount = 0;
@@ -478,11 +522,29 @@ __device__ __forceinline__ void feature_assemble_body(const AssembleArgs& a) {
     K1_MARK(2);
     ipf = __shfl(ipf, qb + 3, 64);
 
+    // ---- score-then-update: who produces this row and who applies the account's events
+    bool seg = false;  // 2..K1_SEG_MAX events of the account in the batch: its first row's quarter owns them
+    if (a.dbuf && has) {
+      h = (int)dh;
+      if (dkey != s) {  // probe collision: walk the chain
+        const DedupTab t = dedup_region(a.dbuf, a.dcap, a.dmax, dedup_ring_region(seq));
+        h = dedup_find(t, s);
+        if (h >= 0) {
+          dfirst = t.first[h];
+          dcount = t.count[h];
+          lrow = t.list[(size_t)h * DEDUP_LIST + ql];
+        }
+      }
+      seg = a.own_short && h >= 0 && dcount >= 2 && dcount <= K1_SEG_MAX;
+    }
+    // rows this quarter produces: its own; all of the account's (leader); none (the leader's do)
+    const int nrows = !seg ? 1 : dfirst == row ? dcount : 0;
+
     // ---- window counts / sums from the tx ring
     int c1 = 0, c5 = 0, c60 = 0;
     long long s60 = 0;
     int hll_dev = 0, hll_ip = 0;
-    if (has) {
+    if (has && nrows > 0) {
       // the amount ring (2 KB per account, half the bytes K1 gathers) is read only where the ts
       // ring shows an entry inside the hour, and not at all for the compat (INCRBY) sum: a
       // third dependent level in exchange for ~half the HBM traffic of the gather (same-box
@@ -535,6 +597,66 @@ __device__ __forceinline__ void feature_assemble_body(const AssembleArgs& a) {
       hll_ip = now < (int64_t)rt.hll_ip_exp ? rt.hll_ip_n : 0;
     }
 
+    // leader: lane k < nrows takes the account's k-th row in row order (the list order is
+    // arbitrary: rank = #smaller entries), reads that row's request and runs its blacklist /
+    // ip-intel probes (the quarter's own probes above cover only its own row). What the per-row
+    // passes below need of row k goes through the quarter's LDS table, not registers held across
+    // them: {row, tx_type, amount, blacklist hit, ip-intel flags}.
+    int(*const sg)[K1_SEG_W] = s_seg[threadIdx.x >> 4];
+    if (nrows > 1) {
+      const int key = ql < nrows ? lrow : (0x7fffffc0 | ql);  // lanes >= nrows: sentinels
+      int rank = 0, mj = row;
+      for (int y = 0; y < K1_QL; ++y) rank += __shfl(key, y, K1_QL) < key;
+      for (int y = 0; y < K1_QL; ++y) {
+        const int ky = __shfl(key, y, K1_QL), ry = __shfl(rank, y, K1_QL);
+        if (ry == ql) mj = ky;
+      }
+      mj = ql < nrows ? min(max(mj, 0), a.n_rows - 1) : row;
+      const uint4* mp = reinterpret_cast<const uint4*>(a.req + mj);
+      const uint4 m0 = mp[0], m1 = mp[1], m2 = mp[2];
+      // {device, fingerprint, ip} against the blacklist, ip against the ip-intel table
+      const uint64_t mk[4] = {((uint64_t)m1.y << 32) | m1.x, ((uint64_t)m1.w << 32) | m1.z,
+                              ((uint64_t)m2.y << 32) | m2.x, ((uint64_t)m2.y << 32) | m2.x};
+      int mhit = 0, mipf = 0;
+      if (tabs) {
+        uint32_t mi[4], mv[4];
+        uint64_t mf[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {  // first probe slots together, then the (rare) walks
+          mi[u] = (uint32_t)mk[u] & (uint32_t)(u < 3 ? c8.y : c8.w);
+          mf[u] = (u < 3 ? a.bl_keys : a.ip_keys)[mi[u]];
+          mv[u] = (u < 3 ? a.bl_exp : a.ip_flags)[mi[u]];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          if (ql >= nrows || mk[u] == 0) continue;
+          const uint64_t* const tk = u < 3 ? a.bl_keys : a.ip_keys;
+          const uint32_t* const tv = u < 3 ? a.bl_exp : a.ip_flags;
+          const uint32_t tmask = (uint32_t)(u < 3 ? c8.y : c8.w);
+          const int max_probe = u < 3 ? c8.z : c9.x;
+          for (int p = 1; p < max_probe && mf[u] != 0 && mf[u] != mk[u]; ++p) {
+            mi[u] = (mi[u] + 1) & tmask;
+            mf[u] = tk[mi[u]];
+            mv[u] = tv[mi[u]];
+          }
+          if (mf[u] == mk[u] && max_probe > 0) {
+            if (u < 3) mhit |= (mv[u] == 0u) || (now < (int64_t)mv[u]);
+            else mipf = (int)mv[u];
+          }
+        }
+      }
+      int* const w = sg[ql];
+      w[0] = mj;
+      w[1] = (int)m0.y;
+      w[2] = (int)m0.z;
+      w[3] = (int)m0.w;
+      w[4] = mhit;
+      w[5] = mipf;
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+
     // ---- assemble raw features (quarter-uniform values)
     FeatRec f{};
     f.tx_count_1m = c1;
@@ -549,7 +671,7 @@ __device__ __forceinline__ void feature_assemble_body(const AssembleArgs& a) {
       if (rt.session_start > 0 && now < (int64_t)rt.session_exp)
         f.session_duration = (int32_t)(now - (int64_t)rt.session_start);
     }
-    int flags = 0;
+    int flags0 = 0;  // the flags the account's state gives (a leader's other rows share them)
     if (has && bt.present) {
       f.total_deposits = bt.total_deposits;
       f.total_withdrawals = bt.total_withdrawals;
@@ -561,38 +683,26 @@ __device__ __forceinline__ void feature_assemble_body(const AssembleArgs& a) {
       f.bonus_claim_count = bt.bonus_claim_count;
       f.bonus_wager_rate = bt.bonus_wager_complete;
       if (bt.bet_count > 0) f.win_rate = (float)((double)bt.win_count / (double)bt.bet_count);
-      if (bt.bonus_claim_count > 3 && bt.total_deposits < 5000) flags |= FR_BONUS_ONLY;
+      if (bt.bonus_claim_count > 3 && bt.total_deposits < 5000) flags0 |= FR_BONUS_ONLY;
     } else {
-      flags |= FR_PARTIAL;
+      flags0 |= FR_PARTIAL;
     }
-    if (ipf & 1) flags |= FR_VPN;
-    if (ipf & 2) flags |= FR_PROXY;
-    if (ipf & 4) flags |= FR_TOR;
-    if (blacklisted) flags |= FR_BLACKLISTED;
+    const int flags = flags0 | k1_row_flags(ipf, blacklisted);
     f.flags = flags;
     f.tx_type = tx_type;
     f.slot = s;
     f.amount = amount;
 
-    // ---- rule pass (engine.go:420-483), raw features
-    int score = 0;
-    uint32_t reasons = 0;
-    if (f.tx_count_1m > cfg.max_tx_per_minute) { score += cfg.w_high_velocity; reasons |= 1u << 0; }
-    if (f.account_age_days < cfg.new_account_days && amount > cfg.large_deposit_amount) {
-      score += cfg.w_new_account_large_tx; reasons |= 1u << 1;
-    }
-    if (f.unique_devices_24h > cfg.max_devices_per_day) { score += cfg.w_multiple_devices; reasons |= 1u << 2; }
-    if (f.unique_ips_24h > cfg.max_ips_per_day) { score += cfg.w_ip_country_mismatch; reasons |= 1u << 3; }
-    if (flags & (FR_VPN | FR_PROXY | FR_TOR)) { score += cfg.w_vpn; reasons |= 1u << 4; }
-    if (f.time_since_last_tx < 300 && tx_type == TX_WITHDRAW) {
-      if (f.deposit_count > 0 && f.total_withdrawals > f.total_deposits * 80 / 100) {
-        score += cfg.w_rapid_deposit_withdraw; reasons |= 1u << 5;
-      }
-    }
-    if (flags & FR_BONUS_ONLY) { score += cfg.w_bonus_abuse; reasons |= 1u << 6; }
-    if (blacklisted) { score += cfg.w_known_fraudster; reasons |= 1u << 7; }
-    f.reserved0 = (int32_t)reasons;
-    f.reserved1 = score > 100 ? 100 : score;
+    // ---- rule pass (engine.go:420-483), raw features: the rules the account's state decides
+    // alone, then the request's (k1_row_rules)
+    K1Rules ru{};
+    if (f.tx_count_1m > cfg.max_tx_per_minute) { ru.score += cfg.w_high_velocity; ru.reasons |= 1u << 0; }
+    if (f.unique_devices_24h > cfg.max_devices_per_day) { ru.score += cfg.w_multiple_devices; ru.reasons |= 1u << 2; }
+    if (f.unique_ips_24h > cfg.max_ips_per_day) { ru.score += cfg.w_ip_country_mismatch; ru.reasons |= 1u << 3; }
+    if (flags0 & FR_BONUS_ONLY) { ru.score += cfg.w_bonus_abuse; ru.reasons |= 1u << 6; }
+    ru.young = f.account_age_days < cfg.new_account_days;
+    ru.rapid = f.time_since_last_tx < 300 && f.deposit_count > 0 && f.total_withdrawals > f.total_deposits * 80 / 100;
+    k1_row_rules(cfg, ru, flags, amount, tx_type, f.reserved0, f.reserved1);
 
     // ---- the 30 model inputs: lane ql produces inputs ql and ql + 16 (raw value selected
     // from the quarter-uniform features, then one pass of each transform for the quarter)
@@ -631,47 +741,109 @@ __device__ __forceinline__ void feature_assemble_body(const AssembleArgs& a) {
     // FeatRec left as 8 single-lane 16-B stores; staged, a wave writes its 4 rows in 2 x 16-B and
     // 1 x 8-B store instructions over contiguous memory
     float* const sx = s_xst[threadIdx.x >> 4];
-    sx[ql] = x0;
-    if (ql + 16 < 30) sx[ql + 16] = x1;
+    uint2* const sf = s_fst[threadIdx.x >> 4];
+    if (nrows > 0) {
+      sx[ql] = x0;
+      if (ql + 16 < 30) sx[ql + 16] = x1;
 #pragma unroll
-    for (int u = 0; u < 7; ++u) {
-      const int j = ql + 16 * u;
-      if (j < ext_w) sx[30 + j] = extv[u];
-    }
-    if (ql == 0) *reinterpret_cast<FeatRec*>(s_fst[threadIdx.x >> 4]) = f;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const int wst = 30 + min(ext_w, 112);
-    if (((wst | (int)a.x_stride) & 3) == 0) {
-      for (int c = ql; c < (wst >> 2); c += K1_QL)
-        reinterpret_cast<float4*>(xr)[c] = reinterpret_cast<const float4*>(sx)[c];
-    } else {
-      for (int c = ql; c < wst; c += K1_QL) xr[c] = sx[c];
-    }
-    for (int j = ql + 112; j < ext_w; j += K1_QL) xr[30 + j] = has ? a.ext[(size_t)s * ext_w + j] : 0.f;
-    K1_MARK(3);
-    reinterpret_cast<uint2*>(a.feat + row)[ql] = s_fst[threadIdx.x >> 4][ql];
-    if (a.fenc)
-      write_fenc(a, row, ql, (rq.tx_type & FV_ENC_BIT) != 0, reinterpret_cast<const uint32_t*>(s_fst[threadIdx.x >> 4]),
-                 s_enc[threadIdx.x >> 4]);
-
-    // ---- score-then-update (engine.go:486-488)
-    if (a.dbuf && has) {
-      const DedupTab t = dedup_region(a.dbuf, a.dcap, a.dmax, dedup_ring_region(seq));
-      h = (int)dh;
-      if (dkey != s) {  // probe collision: walk the chain
-        h = dedup_find(t, s);
-        if (h >= 0) { dfirst = t.first[h]; dcount = t.count[h]; }
+      for (int u = 0; u < 7; ++u) {
+        const int j = ql + 16 * u;
+        if (j < ext_w) sx[30 + j] = extv[u];
       }
-      if (h >= 0) {
-        if (dcount == 1) {
-          apply_event_q(a.upd, cfg, rq, rt, wd, wi, ql, hour_word, s_lc);
+      if (ql == 0) *reinterpret_cast<FeatRec*>(sf) = f;
+    }
+    // one pass for the quarter's own row. A leader goes on with its account's other rows in row
+    // order: the staged X row and FeatRec keep everything the account's state gives, and only
+    // the request's own words are replaced (row k's request and probe results: the LDS table)
+    for (int k = 0; k < nrows; ++k) {
+      int orow = row;
+      bool oenc = (rq.tx_type & FV_ENC_BIT) != 0;
+      if (k > 0) {
+        const int* const w = sg[k];
+        orow = w[0];
+        oenc = (w[1] & FV_ENC_BIT) != 0;
+        if (ql == 0) {
+          const int otype = w[1] & 0xff;
+          const int64_t oamt = (int64_t)(((uint64_t)(uint32_t)w[3] << 32) | (uint32_t)w[2]);
+          const int oflags = flags0 | k1_row_flags(w[5], w[4] != 0);
+          FeatRec* const fr = reinterpret_cast<FeatRec*>(sf);
+          fr->flags = oflags;
+          fr->tx_type = otype;
+          fr->amount = oamt;
+          k1_row_rules(cfg, ru, oflags, oamt, otype, fr->reserved0, fr->reserved1);
+          static_assert(K1_ROW_INPUTS == ((7u << 19) | (15u << 26)), "the model inputs a request decides");
+          sx[19] = (oflags & FR_VPN) ? 1.f : 0.f;
+          sx[20] = (oflags & FR_PROXY) ? 1.f : 0.f;
+          sx[21] = (oflags & FR_TOR) ? 1.f : 0.f;
+          sx[26] = log_transform((float)oamt, id);
+          sx[27] = otype == TX_DEPOSIT ? 1.f : 0.f;
+          sx[28] = otype == TX_WITHDRAW ? 1.f : 0.f;
+          sx[29] = otype == TX_BET ? 1.f : 0.f;
         }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      float* const xo = a.X + (size_t)orow * a.x_stride;
+      const int wst = 30 + min(ext_w, 112);
+      if (((wst | (int)a.x_stride) & 3) == 0) {
+        for (int c = ql; c < (wst >> 2); c += K1_QL)
+          reinterpret_cast<float4*>(xo)[c] = reinterpret_cast<const float4*>(sx)[c];
+      } else {
+        for (int c = ql; c < wst; c += K1_QL) xo[c] = sx[c];
+      }
+      for (int j = ql + 112; j < ext_w; j += K1_QL) xo[30 + j] = has ? a.ext[(size_t)s * ext_w + j] : 0.f;
+      K1_MARK(3);
+      reinterpret_cast<uint2*>(a.feat + orow)[ql] = sf[ql];
+      if (a.fenc)
+        write_fenc(a, orow, ql, oenc, reinterpret_cast<const uint32_t*>(sf), s_enc[threadIdx.x >> 4]);
+      // the next row's words replace staged ones only after this row's reads of them
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+
+    // ---- score-then-update (engine.go:486-488): the account's only event right here; a
+    // leader's events by the whole wave below
+    if (h >= 0 && dcount == 1) apply_event_q(a.upd, cfg, rq, rt, wd, wi, ql, hour_word, s_lc);
+    if (nrows > 1) lead_c = nrows;
+  }
+  // The accounts this wave's quarters lead: every row of theirs is scored (the state reads are
+  // consumed), so the wave applies their events now, one account after the other, with the
+  // update kernel's parallel segment apply (row order, same stored bytes). One memory round trip
+  // per account for all its events, where a chain of per-event applies in the quarter paid one
+  // per event: a 16-event account was a ~40 us tail (Zipf traffic 96 -> 58 M scores/s).
+  if (a.dbuf) {
+    const uint64_t leaders = __ballot(lead_c > 1);
+    if (leaders) {
+      const DedupTab t = dedup_region(a.dbuf, a.dcap, a.dmax, dedup_ring_region(seq));
+      for (int q = 0; q < 4; ++q) {
+        if (!((leaders >> (K1_QL * q)) & 1ull)) continue;  // wave-uniform
+        const int hq = __builtin_amdgcn_readlane(h, K1_QL * q), sq = __builtin_amdgcn_readlane(s, K1_QL * q);
+        const int cq = __builtin_amdgcn_readlane(lead_c, K1_QL * q);
+        apply_list_segment(a.upd, t, hq, cq, sq, load_rt(a.upd.rt + sq), lane);
       }
     }
   }
   K1_MARK(4);
+  // scorer ring: clear the region of batch seq + DEDUP_AHEAD (= seq - 1's, consumed by the state
+  // stage before this one) for its insert; the copy of that batch waits for this batch's state
+  // stage. Spread over the launch's threads (the smallest bucket launches 4 workgroups).
+  if (a.dbuf) {
+    const DedupTab nt = dedup_region(a.dbuf, a.dcap, a.dmax, dedup_ring_region(seq + DEDUP_AHEAD));
+    const int4 m1 = make_int4(-1, -1, -1, -1), big = make_int4(0x7fffffff, 0x7fffffff, 0x7fffffff, 0x7fffffff);
+    const int4 z = make_int4(0, 0, 0, 0);
+    const int gt = (int)(blockIdx.x * 256 + threadIdx.x), nthreads = (int)(gridDim.x * 256);
+    for (int e4 = gt; e4 < (nt.cap >> 2); e4 += nthreads) {
+      reinterpret_cast<int4*>(nt.keys)[e4] = m1;
+      reinterpret_cast<int4*>(nt.first)[e4] = big;
+      reinterpret_cast<int4*>(nt.count)[e4] = z;
+    }
+    if (gt == 0) {
+      nt.ctr[0] = 0;
+      nt.ctr[2] = 0;
+    }
+  }
   if (trow) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     K1_MARK(5);
@@ -1121,6 +1293,12 @@ __device__ void apply_segment_wave(const UpdateArgs& a, const DedupTab& t, int h
     apply_scan_chunks(a, t, s, r, lane, lr, c);
     return;
   }
+  apply_list_segment(a, t, h, c, s, r, lane);
+}
+
+// the c (2..DEDUP_LIST) events of account s from its dedup list, in row order, by one wave (the
+// update kernel's waves, and K1's for the accounts its quarters lead)
+__device__ void apply_list_segment(const UpdateArgs& a, const DedupTab& t, int h, int c, int s, AcctRT r, int lane) {
   // sort the (distinct) row indices: rank = #smaller, then push each to lane `rank`
   // sc1 load: the entries come from other waves of the same launch (feature_assemble hand-off)
   const int raw = __hip_atomic_load(&t.list[(size_t)h * DEDUP_LIST + lane], __ATOMIC_RELAXED,
@@ -1138,11 +1316,10 @@ constexpr int UPD_MULTI_BLOCKS = 64;  // 256 waves loop over the list (any count
 // dependent memory round trips per account: {list count, first pair} -> {count, AcctRT, row
 // list} -> request rows -> both HLL registers -> stores (the pair carries the account slot, so
 // count, AcctRT and the row list are loaded together)
-// The multi-event accounts: wave w0 of `nwaves` loops over the region's list; thread `gt` of
-// `nthreads` also clears the dedup region batch seq + DEDUP_AHEAD will insert into (scorer ring).
+// The multi-event accounts: wave w0 of `nwaves` loops over the region's list (never launched
+// behind a K1 that owned them: AssembleArgs::own_short).
 template <int WPB>
-__device__ __forceinline__ void update_multi_body(const UpdateArgs& a, int w0, int nwaves, int gt, int nthreads,
-                                                  uint32_t (*s_regs)[128]) {
+__device__ __forceinline__ void update_multi_body(const UpdateArgs& a, int w0, int nwaves, uint32_t (*s_regs)[128]) {
   const int lane = threadIdx.x & 63;
   const DedupTab t = upd_region(a);
   const int npair = t.nmax >> 1;
@@ -1161,28 +1338,12 @@ __device__ __forceinline__ void update_multi_body(const UpdateArgs& a, int w0, i
     if (c > DEDUP_LIST && a.region < 0) continue;  // scorer path: the hot workgroups of update_segments_kernel apply it
     apply_segment_wave(a, t, h, c, s, r, lane, s_regs[(threadIdx.x >> 6) & (WPB - 1)]);
   }
-  // scorer ring: clear the region of batch seq + DEDUP_AHEAD (= seq-1's, consumed by now) for
-  // its insert; the copy of that batch waits for this batch's state stage
-  if (a.region < 0) {
-    const DedupTab nt = dedup_region(a.dbuf, a.dcap, a.dmax, dedup_ring_region(a.hdr->seq + DEDUP_AHEAD));
-    const int4 m1 = make_int4(-1, -1, -1, -1), big = make_int4(0x7fffffff, 0x7fffffff, 0x7fffffff, 0x7fffffff);
-    const int4 z = make_int4(0, 0, 0, 0);
-    for (int e4 = gt; e4 < (nt.cap >> 2); e4 += nthreads) {
-      reinterpret_cast<int4*>(nt.keys)[e4] = m1;
-      reinterpret_cast<int4*>(nt.first)[e4] = big;
-      reinterpret_cast<int4*>(nt.count)[e4] = z;
-    }
-    if (gt == 0) {
-      nt.ctr[0] = 0;
-      nt.ctr[2] = 0;
-    }
-  }
 }
 
 __global__ void __launch_bounds__(256) update_multi_kernel(UpdateArgs a) {
   __shared__ uint32_t s_regs[4][128];  // per wave: a multi-event account's HLL registers
   const int w0 = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
-  update_multi_body<4>(a, w0, UPD_MULTI_BLOCKS * 4, blockIdx.x * 256 + threadIdx.x, UPD_MULTI_BLOCKS * 256, s_regs);
+  update_multi_body<4>(a, w0, UPD_MULTI_BLOCKS * 4, s_regs);
 }
 
 // Hot accounts on the scorer path (more than DEDUP_LIST events in one batch: Zipf traffic gives
@@ -1360,8 +1521,7 @@ __global__ void __launch_bounds__(HOT_THREADS) update_segments_kernel(UpdateArgs
   const int b = (int)blockIdx.x;
   if (b < UPD_SEG_MULTI) {
     const int w0 = __builtin_amdgcn_readfirstlane(b * (HOT_THREADS / 64) + (int)(threadIdx.x >> 6));
-    update_multi_body<HOT_THREADS / 64>(a, w0, UPD_SEG_MULTI * (HOT_THREADS / 64), b * HOT_THREADS + threadIdx.x,
-                                        UPD_SEG_MULTI * HOT_THREADS, L.regs);
+    update_multi_body<HOT_THREADS / 64>(a, w0, UPD_SEG_MULTI * (HOT_THREADS / 64), L.regs);
   } else {
     update_hot_body(a, b - UPD_SEG_MULTI, HOT_BLOCKS, L.hot);
   }

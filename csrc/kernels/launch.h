@@ -12,10 +12,15 @@ namespace igp {
 
 // events of one account per batch held in its dedup list (more: ordered scan of the batch)
 constexpr int DEDUP_LIST = 64;
+// scorer path, a batch in which no account has more events than this (AssembleArgs::own_short):
+// every multi-event account is scored and applied inside K1, led by the quarter-wave of its first
+// row (one list entry per lane), and no update_segments launch follows
+constexpr int K1_SEG_MAX = 16;
+static_assert(K1_SEG_MAX <= DEDUP_LIST, "K1 reads a short account's rows from its dedup list");
 
-// scorer batches rotate over DEDUP_RING dedup regions by BatchHdr::seq: batch q's state stage
-// clears the region of batch q + DEDUP_AHEAD (= q - 1's, consumed by then), so batch q+1's dedup
-// insert (copy stream) can run while batch q is still in K1 / update_segments on the state stream.
+// scorer batches rotate over DEDUP_RING dedup regions by BatchHdr::seq: batch q's K1 clears the
+// region of batch q + DEDUP_AHEAD (= q - 1's, consumed by then), so batch q+1's dedup insert
+// (copy stream) can run while batch q is still in K1 / update_segments on the state stream.
 // The copy of batch q waits for the state stage of batch q - DEDUP_AHEAD (the native driver keeps
 // one post-state event per ring entry and only queues the wait when the host does not already see
 // that batch complete). Eight regions let the pipeline run up to seven batches deep without that
@@ -89,13 +94,19 @@ struct AssembleArgs {
   int32_t* dbuf;            // dedup regions (nullable: no score-then-update)
   int32_t dcap;
   int32_t dmax;
+  // 1: K1 owns the accounts with 2..K1_SEG_MAX events in the batch (scores all their rows and
+  // applies their events); only for a batch in which no account has more, with no update_segments
+  // launch behind it. 0: such accounts are scored per row and applied by update_segments.
+  int32_t own_short;
   int32_t x_stride;
   int32_t ring_size;
   int32_t n_rows;           // rows covered by the launch (graph bucket)
   int64_t* trace;           // [8 waves][8] phase timestamps (nullable; tools/kbench.py --trace)
   // score-then-update (dbuf != null): the batch's dedup insert ran before K1 (dedup_insert);
-  // each wave applies its request's event when it is the account's only one in the batch
-  // and opens the segment of a multi-event account (applied by update_segments after K1)
+  // each quarter-wave applies its request's event when it is the account's only one in the
+  // batch; with own_short, an account's first row also applies all of its 2..K1_SEG_MAX events;
+  // the other multi-event accounts are applied by update_segments after K1. K1 also clears the
+  // region of batch seq + DEDUP_AHEAD.
   UpdateArgs upd;
 };
 
@@ -103,9 +114,11 @@ struct AssembleArgs {
 void launch_feature_assemble(const AssembleArgs& a, hipStream_t st);
 // standalone event ingestion (event bus / history replay): reset + insert + single + segments
 void launch_feature_update(const UpdateArgs& a, hipStream_t st);
-// scorer path: dedup insert of the batch (before K1; K1 applies single-event accounts) ...
+// scorer path: dedup insert of the batch (before K1; K1 applies the single-event accounts, and
+// with own_short every account of a batch whose accounts have at most K1_SEG_MAX events) ...
 void launch_dedup_insert(const UpdateArgs& a, hipStream_t st);
-// ... and the tail after K1: segment fill + per-account wave apply of multi-event accounts
+// ... and the tail after K1: per-account apply of the multi-event accounts (not launched by the
+// native driver behind an own_short K1)
 void launch_update_segments(const UpdateArgs& a, hipStream_t st);
 
 // ---- K2 tree ensemble (complete layout)

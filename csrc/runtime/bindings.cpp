@@ -18,6 +18,7 @@
 #include "cpu_scorer.h"
 #include "serve_core.h"
 #include "link_index.h"
+#include "mult_sketch.h"
 #include "executor.h"
 #include "onnx_model.h"
 #include "sampler.h"
@@ -354,6 +355,31 @@ PYBIND11_MODULE(_native, m) {
         d["ip_hash"] = vec_np(b.ip_hash);
         return d;
       });
+
+  // the serving core's bound on one account's rows in a step (mult_sketch.h): `slots` holds the
+  // rows of the step's items back to back, `sizes` the rows per item. Each item is sketched as
+  // on the ingress threads, the items are combined as in the stepper.
+  m.attr("K1_SEG_MAX") = IGP_K1_SEG_MAX;
+  m.def("mult_step_bound", [](py::array_t<int32_t, py::array::c_style | py::array::forcecast> slots,
+                              std::vector<int64_t> sizes) {
+    const int32_t* sp = slots.data();
+    const int64_t total = slots.size();
+    std::vector<MultSketch> items(sizes.size());
+    std::vector<ReqRec> rows;
+    int64_t at = 0;
+    for (size_t i = 0; i < sizes.size(); ++i) {
+      if (sizes[i] < 0 || at + sizes[i] > total) throw std::runtime_error("mult_step_bound: sizes exceed slots");
+      rows.assign(size_t(sizes[i]), ReqRec{});
+      for (int64_t k = 0; k < sizes[i]; ++k) rows[size_t(k)].slot = sp[at + k];
+      items[i].build(rows.data(), rows.size());
+      at += sizes[i];
+    }
+    if (at != total) throw std::runtime_error("mult_step_bound: sizes do not cover slots");
+    std::vector<const MultSketch*> parts;
+    for (const MultSketch& it : items) parts.push_back(&it);
+    std::vector<uint32_t> scratch;
+    return mult_step_bound(parts.data(), parts.size(), scratch);
+  }, py::arg("slots"), py::arg("sizes"));
 
   m.def("tx_type_id", [](const std::string& s) { return int(wire::tx_type_id(s.data(), s.size())); });
   // batch identifier digests (utils/hashing.id_hash semantics: "" -> 0, a real 0 -> 1)

@@ -50,7 +50,7 @@ int32_t CpuDevice::submit_fn(void* ctx, int32_t slot, int32_t n, int32_t, int64_
   auto* d = static_cast<CpuDevice*>(ctx);
   Slot& s = d->slots_[slot];
   try {
-    s.wf = wf != 0;
+    s.wf = (wf & IGP_SUBMIT_WANT_FEATURES) != 0;  // (IGP_SUBMIT_NO_UPDATE: nothing to skip here)
     d->sc_->score(s.rows.data(), size_t(n), now, true, s.res.data(), s.wf ? s.feat.data() : nullptr);
   } catch (const std::exception& e) {
     set_err(err, errlen, e.what());

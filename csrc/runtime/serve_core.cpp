@@ -1,4 +1,5 @@
 #include "serve_core.h"
+#include "mult_sketch.h"
 #include "thread_name.h"
 
 #include <algorithm>
@@ -50,6 +51,7 @@ struct ServeCore::Item {
   int64_t aborted_rows = 0;     // rows that never reached a step (abort; m)
   int64_t now = 0;
   bool wf = false;
+  MultSketch mult;              // bound on one account's rows among `rows` (direct mode; else unknown)
   ResultRec* res = nullptr;     // outputs in request order
   FeatRec* feat = nullptr;
   ResultRec res1{};             // unary storage
@@ -152,6 +154,8 @@ void ServeCore::resolve_rows(std::vector<wire::TxRow>& rows, Item* it) {
     }
     it->ocur.assign(1, 0);
     it->ostart = {0, int32_t(n)};  // one owner (a world-1 exchange reads the owner ranges too)
+    // here, on the ingress threads, not in the stepper: the stepper only combines (issue_step)
+    if (!exchange_) it->mult.build(it->rows.data(), n);
   } else {
     // counting sort by owner (owner = digest % world, the registry's routing)
     it->ostart.assign(world_ + 1, 0);
@@ -258,12 +262,18 @@ std::string_view ServeCore::score_batch_view(const char* data, size_t n, int64_t
   // ingress threads' samples; same-box A/B 4 runs each: 121.7 vs 114.8 M scores/s, p99 1.47 vs
   // 1.79 ms, profiles/r5/host); the item is done with its rows when wait_item returns
   thread_local std::vector<ReqRec> rows_buf;
+  thread_local std::vector<uint16_t> mult_buf;  // (the item's sketch counters, likewise)
   it.rows.swap(rows_buf);
+  it.mult.c.swap(mult_buf);
   struct GiveBack {
     std::vector<ReqRec>& buf;
+    std::vector<uint16_t>& mbuf;
     Item& item;
-    ~GiveBack() { buf.swap(item.rows); }
-  } give_back{rows_buf, it};
+    ~GiveBack() {
+      buf.swap(item.rows);
+      mbuf.swap(item.mult.c);
+    }
+  } give_back{rows_buf, mult_buf, it};
   it.kind = 0;
   it.now = now >= 0 ? now : wall_s();
   it.wf = opt_.features;
@@ -308,6 +318,7 @@ void ServeCore::score_rows(const ReqRec* rows, const int32_t* owners, size_t n, 
     it.rows.assign(rows, rows + n);
     it.ocur.assign(1, 0);
     it.ostart = {0, int32_t(n)};
+    if (!exchange_) it.mult.build(it.rows.data(), n);
   } else {
     if (!owners) throw std::runtime_error("ServeCore.score_rows: owners required when world > 1");
     it.ostart.assign(world_ + 1, 0);
@@ -624,13 +635,24 @@ bool ServeCore::issue_step(std::unique_lock<std::mutex>& lk, bool allow_empty) {
       std::memcpy(chunks + size_t(s.owner) * stride + 1 + s.dev_pos, s.item->rows.data() + s.item_pos,
                   size_t(s.count) * sizeof(ReqRec));
   }
+  // can an account have more rows in this step than the device's K1 applies by itself? The
+  // items' sketches say no for almost every step of spread traffic; the device then skips its
+  // multi-event update launch (device_ops.h IGP_SUBMIT_NO_UPDATE). Timed with the pack.
+  int32_t flags = st->wf ? IGP_SUBMIT_WANT_FEATURES : 0;
+  if (!exchange_) {
+    thread_local std::vector<const MultSketch*> parts;
+    thread_local std::vector<uint32_t> scratch;
+    parts.clear();
+    for (const Seg& s : st->segs) parts.push_back(&s.item->mult);
+    if (mult_step_bound(parts.data(), parts.size(), scratch) <= IGP_K1_SEG_MAX) flags |= IGP_SUBMIT_NO_UPDATE;
+  }
   const int64_t t1 = now_ns();
   // the step is announced before the launch: an exchange device may block inside submit until
   // every peer reached this step, and an idle peer only issues it once it sees us ahead
   const int64_t issued = issued_.fetch_add(1) + 1;
   if (clock_) clock_->post(issued);
   char err[256] = {0};
-  const int rc = dev_->submit(dev_->ctx, slot, n, seq, now, st->wf ? 1 : 0, err, sizeof err);
+  const int rc = dev_->submit(dev_->ctx, slot, n, seq, now, flags, err, sizeof err);
   const int64_t t2 = now_ns();
   st->t_submit = t2;
   if (rc != 0) {

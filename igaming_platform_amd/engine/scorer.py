@@ -277,12 +277,14 @@ class GpuScorer:
         K.memcpy_async(sb.dev_slab, self.host_slab[slot], HDR_BYTES + REQ_BYTES * bucket)
 
     def _state_body(self, slot: int, bucket: int, part: str = "all") -> None:
-        """K1 (part "k1"), then the multi-event update that also clears the dedup region of
-        batch seq + DEDUP_AHEAD (part "update")."""
+        """K1 (part "k1"), which also clears the dedup region of batch seq + DEDUP_AHEAD, then the
+        multi-event update (part "update"). Part "k1own": the K1 that scores and applies the short
+        multi-event accounts itself, for batches the native driver issues without the update."""
         sb, upd = self.slots[slot], self.update_features
-        if part in ("all", "k1"):
+        if part in ("all", "k1", "k1own"):
             route = self._fenc_route(slot, bucket)
             K.feature_assemble(self.store, sb.hdr, self.cfg_dev, sb.req, sb.X, sb.feat, bucket, dedup=upd,
+                               own_short=upd and part == "k1own",
                                fenc=None if route is not None else self._fenc_out(slot), fenc_route=route)
         if upd and part in ("all", "update"):
             K.update_segments(self.store, self.cfg_dev, sb.req, bucket, sb.hdr)
@@ -375,13 +377,14 @@ class GpuScorer:
                                          lambda: self._state_body(slot, b, "k1" if split else "all"),
                                          lambda: self._model_body(slot, b),
                                          lambda: self._model_body(slot, b, with_features=True),
-                                         lambda: self._state_body(slot, b, "update")):
+                                         lambda: self._state_body(slot, b, "update"),
+                                         lambda: self._state_body(slot, b, "k1own")):
                                 with K.Recorder() as r:
                                     body()
                                 lists.append(r.ops)
                             d.set_ops(b, slot, *lists[:4])
                             if split:
-                                d.set_state_update(b, slot, lists[4])
+                                d.set_state_update(b, slot, lists[4], lists[5])
             # (round 5 removed the one-stream serial mode - cfg2 22.6 vs 11.0 M, cfg3 107 vs 57 M,
             # profiles/r2/serial - and the asynchronous issue thread - cfg3 118 vs 127 M,
             # profiles/r2/direct3: both measured slower)

@@ -116,7 +116,7 @@ def _host_or_dev(t: Optional[torch.Tensor], name: str, min_numel: int, device, d
 
 # --------------------------------------------------------------------------- K1
 def feature_assemble(store, hdr: torch.Tensor, cfg_dev: torch.Tensor, req: torch.Tensor,
-                     X: torch.Tensor, feat: torch.Tensor, n_rows: int, dedup: bool = False,
+                     X: torch.Tensor, feat: torch.Tensor, n_rows: int, dedup: bool = False, own_short: bool = False,
                      trace: Optional[torch.Tensor] = None, fenc: Optional[torch.Tensor] = None,
                      fenc_route: Optional[dict] = None) -> None:
     """K1. ``dedup=True``: score-then-update. :func:`dedup_insert` must have registered the
@@ -151,6 +151,9 @@ def feature_assemble(store, hdr: torch.Tensor, cfg_dev: torch.Tensor, req: torch
         trace=_opt(trace, "trace", dtype=torch.int64, min_numel=((int(n_rows) + 15) // 16) * 64, device=dev),
     )
     if dedup:
+        # own_short: K1 also scores and applies the accounts with 2..K1_SEG_MAX events (then no
+        # update_segments may follow for them: the native driver pairs this form with a skipped launch)
+        d["own_short"] = 1 if own_short else 0
         d["upd"] = update_args(store, cfg_dev, req, n_rows, hdr=hdr, region=-1)
     if fenc_route is not None:
         if fenc is not None:
