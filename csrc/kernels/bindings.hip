@@ -359,6 +359,30 @@ PYBIND11_MODULE(_hipk, m) {
     if (a.op == 1 && a.nb < 1) throw std::runtime_error("join: concat widths");
     launch_or_record([a](hipStream_t st) { launch_join(a, st); }, s, "join");
   });
+  m.def("row_op", [](py::dict d, uintptr_t s) {
+    RowArgs a{};
+    a.X = ptr<const void*>(d, "X");
+    a.Y = ptr<void*>(d, "Y");
+    a.gamma = ptr<const float*>(d, "gamma");
+    a.beta = ptr<const float*>(d, "beta");
+    a.m_ptr = ptr<const int32_t*>(d, "m_ptr");
+    a.M = geti(d, "M");
+    a.N = geti(d, "N");
+    a.ldx = geti(d, "ldx");
+    a.ldy = geti(d, "ldy");
+    a.x_bf16 = geti(d, "x_bf16");
+    a.y_bf16 = geti(d, "y_bf16");
+    a.op = geti(d, "op");
+    a.act = geti(d, "act");
+    a.p0 = d.contains("p0") ? d["p0"].cast<float>() : 0.f;
+    a.p1 = d.contains("p1") ? d["p1"].cast<float>() : 0.f;
+    a.eps = d.contains("eps") ? d["eps"].cast<float>() : 0.f;
+    if (!a.X || !a.Y || a.N < 1 || a.M < 0 || a.ldx < a.N || a.ldy < a.N) throw std::runtime_error("row_op: args");
+    if (a.op < ROW_LAYERNORM || a.op > ROW_ACT) throw std::runtime_error("row_op: op");
+    if (a.op == ROW_LAYERNORM && (!a.gamma || !(a.eps >= 0.f))) throw std::runtime_error("row_op: layernorm needs gamma and eps >= 0");
+    if (a.op == ROW_ACT && (a.act < RA_RELU || a.act > RA_PRELU)) throw std::runtime_error("row_op: act code");
+    launch_or_record([a](hipStream_t st) { launch_row(a, st); }, s, "row_op");
+  });
 
   auto head_args = [](const py::dict& d) {
     HeadArgs a{};

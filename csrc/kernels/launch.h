@@ -217,6 +217,29 @@ struct JoinArgs {
 };
 void launch_join(const JoinArgs& a, hipStream_t st);
 
+// Row ops on one [M][N] activation tensor (rowops.hip): layernorm and softmax over each row,
+// and the elementwise activations the dense / head epilogues do not carry
+enum RowOp : int32_t { ROW_LAYERNORM = 0, ROW_SOFTMAX = 1, ROW_ACT = 2 };
+// act codes 0-3 are the dense epilogue's (GemmArgs::act)
+enum RowAct : int32_t { RA_NONE = 0, RA_RELU = 1, RA_SIGMOID = 2, RA_TANH = 3, RA_LEAKY_RELU = 4, RA_ELU = 5,
+                        RA_SELU = 6, RA_SOFTPLUS = 7, RA_HARD_SIGMOID = 8, RA_GELU = 9, RA_GELU_TANH = 10,
+                        RA_CLIP = 11, RA_PRELU = 12 };
+struct RowArgs {
+  const void* X;            // [M][ldx] f32 or bf16
+  void* Y;                  // [M][ldy] f32 or bf16
+  const float* gamma;       // [N]: layernorm scale (required); prelu per-column slope (nullable -> p0)
+  const float* beta;        // [N]: layernorm bias (nullable)
+  const int32_t* m_ptr;     // live rows in device memory (nullable -> M)
+  int32_t M, N;
+  int32_t ldx, ldy;
+  int32_t x_bf16, y_bf16;
+  int32_t op;               // RowOp
+  int32_t act;              // RowAct (op ROW_ACT)
+  float p0, p1;             // act parameters: alpha | alpha, gamma (selu) | alpha, beta (hard_sigmoid) | lo, hi (clip)
+  float eps;                // layernorm
+};
+void launch_row(const RowArgs& a, hipStream_t st);
+
 // dense(N1) + act1 + dense(N1 -> 1) + act2 fused; W1 bf16 [N1_pad(64)][k_pad(32)]
 // ---- K5 ensemble + action + metrics
 struct HeadArgs {

@@ -275,6 +275,63 @@ void lstm(const onnx::Node& n, const Tensor& X, const Tensor& W, const Tensor& R
   }
 }
 
+// ---- normalisations and activations of framework-exported MLPs (PyTorch / Keras): statistics
+// and transcendental arguments in double, outputs float.
+
+// BatchNormalization, inference form: X [N][C][...] with per-channel scale, B, mean, var.
+Tensor batch_norm(const onnx::Node& n, const Tensor& X, const Tensor& scale, const Tensor& B, const Tensor& mean,
+                  const Tensor& var) {
+  if (n.geti("training_mode", 0) != 0)
+    throw std::runtime_error("BatchNormalization: training_mode=1 is not supported (inference only)");
+  if (X.dims.size() < 2) throw std::runtime_error("BatchNormalization: X must have a channel axis (rank >= 2)");
+  const int64_t C = X.dims[1];
+  for (const Tensor* t : {&scale, &B, &mean, &var})
+    if (t->numel() != C) throw std::runtime_error("BatchNormalization: scale / B / mean / var must hold one value per channel");
+  const double eps = n.getf("epsilon", 1e-5f);
+  const auto x = as_float(X), s = as_float(scale), b = as_float(B), m = as_float(mean), v = as_float(var);
+  int64_t inner = 1;
+  for (size_t d = 2; d < X.dims.size(); ++d) inner *= X.dims[d];
+  Tensor out = make(X.dims);
+  for (int64_t e = 0; e < X.numel(); ++e) {
+    const int64_t c = (e / inner) % C;
+    out.f[e] = float((double(x[e]) - m[c]) / std::sqrt(double(v[c]) + eps) * s[c] + b[c]);
+  }
+  return out;
+}
+
+// LayerNormalization over the last axis: two passes (mean, then squared deviations) in double.
+Tensor layer_norm(const onnx::Node& n, const Tensor& X, const Tensor& scale, const Tensor* B) {
+  const int64_t rank = int64_t(X.dims.size());
+  const int64_t axis = n.geti("axis", -1);
+  if (rank < 1 || (axis != -1 && axis != rank - 1))
+    throw std::runtime_error("LayerNormalization: axis " + std::to_string(axis) + " is not supported (last axis only)");
+  const int64_t C = X.dims.back();
+  if (scale.numel() != C) throw std::runtime_error("LayerNormalization: Scale must hold one value per column");
+  if (B && B->numel() != C) throw std::runtime_error("LayerNormalization: B must hold one value per column");
+  const double eps = n.getf("epsilon", 1e-5f);
+  const auto x = as_float(X), s = as_float(scale);
+  const std::vector<float> b = B ? as_float(*B) : std::vector<float>();
+  Tensor out = make(X.dims);
+  for (int64_t r = 0; r < X.numel() / std::max<int64_t>(C, 1); ++r) {
+    const float* z = &x[r * C];
+    double mu = 0, ss = 0;
+    for (int64_t c = 0; c < C; ++c) mu += z[c];
+    mu /= double(C);
+    for (int64_t c = 0; c < C; ++c) ss += (z[c] - mu) * (z[c] - mu);
+    const double inv = 1.0 / std::sqrt(ss / double(C) + eps);
+    for (int64_t c = 0; c < C; ++c) out.f[r * C + c] = float((z[c] - mu) * inv * s[c] + (B ? double(b[c]) : 0.0));
+  }
+  return out;
+}
+
+inline float softplus(float x) { return float(std::max(double(x), 0.0) + std::log1p(std::exp(-std::fabs(double(x))))); }
+
+float gelu(float xf, bool tanh_form) {
+  const double x = xf;
+  if (tanh_form) return float(0.5 * x * (1.0 + std::tanh(0.7978845608028654 * (x + 0.044715 * x * x * x))));
+  return float(0.5 * x * (1.0 + std::erf(x * 0.7071067811865476)));
+}
+
 // ---- ai.onnx.ml linear models and preprocessing (sklearn-style pipelines: Scaler ->
 // LinearClassifier -> ZipMap; Normalizer; LinearRegressor). Semantics follow the ai.onnx.ml
 // operator definitions; ORT itself is not available offline, so exact ORT parity is unpinned
@@ -425,6 +482,13 @@ std::map<std::string, Tensor> Executor::run(const std::map<std::string, Tensor>&
     if (i >= n.inputs.size() || n.inputs[i].empty()) return nullptr;
     return &get(n.inputs[i]);
   };
+  auto is_read = [&](const std::string& name) {  // by a node or as a graph output
+    for (auto& m : g.nodes)
+      if (std::find(m.inputs.begin(), m.inputs.end(), name) != m.inputs.end()) return true;
+    for (auto& v : g.outputs)
+      if (v.name == name) return true;
+    return false;
+  };
   for (size_t k : order_) {
     const auto& n = g.nodes[k];
     const std::string& op = n.op_type;
@@ -454,6 +518,54 @@ std::map<std::string, Tensor> Executor::run(const std::map<std::string, Tensor>&
       if (n.attr("min")) lo = n.getf("min", lo);
       if (n.attr("max")) hi = n.getf("max", hi);
       out = unary(get(n.inputs[0]), [lo, hi](float x) { return std::min(std::max(x, lo), hi); });
+    } else if (op == "Elu") {
+      const double a = n.getf("alpha", 1.f);
+      out = unary(get(n.inputs[0]), [a](float x) { return x > 0 ? x : float(a * std::expm1(double(x))); });
+    } else if (op == "Selu") {
+      const double a = n.getf("alpha", 1.67326319217681884765625f), g2 = n.getf("gamma", 1.05070102214813232421875f);
+      out = unary(get(n.inputs[0]), [a, g2](float x) { return float(x > 0 ? g2 * x : g2 * a * std::expm1(double(x))); });
+    } else if (op == "Softplus") {
+      out = unary(get(n.inputs[0]), softplus);
+    } else if (op == "HardSigmoid") {
+      const double a = n.getf("alpha", 0.2f), b = n.getf("beta", 0.5f);
+      out = unary(get(n.inputs[0]), [a, b](float x) { return float(std::min(1.0, std::max(0.0, a * x + b))); });
+    } else if (op == "Gelu") {
+      const std::string ap = n.gets("approximate", "none");
+      if (ap != "none" && ap != "tanh") throw std::runtime_error("Gelu: approximate must be none or tanh, got " + ap);
+      const bool th = ap == "tanh";
+      out = unary(get(n.inputs[0]), [th](float x) { return gelu(x, th); });
+    } else if (op == "PRelu") {
+      if (n.inputs.size() < 2) throw std::runtime_error("PRelu: needs X and slope");
+      const Tensor& x = get(n.inputs[0]);
+      const Tensor& sl = get(n.inputs[1]);
+      const int64_t C = x.dims.empty() ? 1 : x.dims.back();
+      if (sl.numel() != 1 && (sl.numel() != C || (!sl.dims.empty() && sl.dims.back() != C)))
+        throw std::runtime_error("PRelu: slope must be a scalar or one value per column");
+      const auto s = as_float(sl), xf = as_float(x);
+      out = make(x.dims);
+      for (int64_t e = 0; e < x.numel(); ++e) out.f[e] = xf[e] >= 0 ? xf[e] : s[s.size() == 1 ? 0 : e % C] * xf[e];
+    } else if (op == "BatchNormalization") {
+      if (n.inputs.size() < 5) throw std::runtime_error("BatchNormalization: needs X, scale, B, mean and var");
+      out = batch_norm(n, get(n.inputs[0]), get(n.inputs[1]), get(n.inputs[2]), get(n.inputs[3]), get(n.inputs[4]));
+    } else if (op == "LayerNormalization") {
+      if (n.inputs.size() < 2 || n.inputs[1].empty()) throw std::runtime_error("LayerNormalization: Scale is required");
+      for (size_t o = 1; o < n.outputs.size(); ++o)
+        if (!n.outputs[o].empty() && is_read(n.outputs[o]))
+          throw std::runtime_error("LayerNormalization: the Mean / InvStdDev outputs are not produced");
+      out = layer_norm(n, get(n.inputs[0]), get(n.inputs[1]), opt(n, 2));
+    } else if (op == "Dropout") {
+      // inference: the identity; a constant true training_mode would make it random
+      if (n.inputs.size() > 2 && !n.inputs[2].empty()) {
+        auto it = g.initializers.find(n.inputs[2]);
+        if (it != g.initializers.end() && it->second.numel() > 0 && as_int(it->second)[0] != 0)
+          throw std::runtime_error("Dropout: training_mode is a constant true (inference only)");
+      }
+      out = get(n.inputs[0]);
+      if (n.outputs.size() > 1 && !n.outputs[1].empty() && is_read(n.outputs[1])) {
+        Tensor mask = make(out.dims);
+        std::fill(mask.f.begin(), mask.f.end(), 1.f);
+        vals[n.outputs[1]] = std::move(mask);
+      }
     } else if (op == "Cast") {
       int64_t to = n.geti("to", FLOAT);
       const Tensor& x = get(n.inputs[0]);

@@ -128,9 +128,11 @@ class DeviceModel:
         for i, s in enumerate(steps):
             last = i == len(steps) - 1
             cons = self.consumers[i]
-            feeds_mma = (not last) and bool(cons) and all(steps[j].kind in ("dense", "head", "join") for j in cons)
-            # bf16 plans hand bf16 activations to the MFMA layers reading them; fp32 plans stay f32
-            dt = (torch.bfloat16 if (s.kind in ("dense", "gru", "lstm", "join") and feeds_mma and plan.precision == "bf16")
+            feeds_mma = (not last) and bool(cons) and all(steps[j].kind in ("dense", "head", "join", "row") for j in cons)
+            # bf16 plans hand bf16 activations to the MFMA layers reading them (joins and row steps
+            # pass them on in the same dtype); fp32 plans stay f32
+            dt = (torch.bfloat16 if (s.kind in ("dense", "gru", "lstm", "join", "row") and feeds_mma
+                                     and plan.precision == "bf16")
                   else torch.float32)
             self.step_out.append(torch.zeros((B, s.out_width), dtype=dt, device=self.device))
             if s.kind == "tree":
@@ -219,6 +221,10 @@ class DeviceModel:
                 K.tree_ensemble(s, cur, None if fuse else out, bucket, partial=self.tree_partial,
                                 groups=g, no_finish=fuse, ens=ens if i == len(steps) - 1 else None)
                 fused_partial = (self.tree_partial, g, s) if fuse else None
+            elif s.kind == "row":  # layernorm / softmax / an activation with no dense layer to ride on
+                K.row_op(s.op, cur, out, bucket, s.width, act=s.act, p0=s.p0, p1=s.p1, eps=s.eps, gamma=s.gamma,
+                         beta=s.beta, m_ptr=m_ptr)
+                fused_partial = None
             elif s.kind == "dense":
                 K.dense(cur, s.w, s.b, out, bucket, s.n, s.k, act=s.act, m_ptr=m_ptr)
             elif s.kind == "head":

@@ -16,6 +16,14 @@ steps:
 * ``LSTMStep``   ONNX LSTM (same directions / layouts, default activations, no peepholes) -> K4
                  ``lstm`` (csrc/kernels/lstm.hip).
 * ``JoinStep``   Add / Concat of two branches (residual blocks, wide & deep) -> ``join``.
+* ``RowStep``    LayerNormalization (last axis), Softmax (feature axis), the activations the
+                 dense epilogue does not carry (LeakyRelu, Elu, Selu, Softplus, HardSigmoid, Gelu,
+                 PRelu, Clip) and a Relu / Sigmoid / Tanh with no dense layer to fold into (after
+                 a join, a tree, another activation) -> ``row_op`` (csrc/kernels/rowops.hip).
+                 A Softmax over the two logits of an exclusive dense layer is narrowed to
+                 sigmoid(z1 - z0) instead, so a two-logit classifier runs on the fused head.
+* ``BatchNormalization`` (inference) is a per-column affine and folds like ``Scaler``;
+  ``Dropout`` is folded away.
 * ai.onnx.ml ``LinearClassifier`` / ``LinearRegressor`` (post NONE / LOGISTIC; a two-class
   SOFTMAX as sigmoid(s1 - s0)) -> a dense layer, so an sklearn pipeline
   Scaler -> LinearClassifier -> ZipMap, or an MLP ending in one, runs on the fused head.
@@ -255,6 +263,8 @@ class Plan:
                 parts.append(f"head({s.k}->{s.n1},{s.act1}->1,{s.act2})")
             elif s.kind == "join":
                 parts.append(f"{s.op}(#{s.a},#{s.b})")
+            elif s.kind == "row":
+                parts.append(f"{s.act if s.op == 'act' else s.op}({s.width})")
             else:
                 parts.append(f"{s.kind}(I={s.in_dim},H={s.hidden})")
         return " -> ".join(parts)
@@ -275,6 +285,30 @@ class JoinStep:
     @property
     def out_width(self) -> int:
         return self.na if self.op == "add" else self.na + self.nb
+
+
+@dataclass
+class RowStep:
+    """A row op on one activation tensor (rowops.hip): ``layernorm`` (gamma, optional beta, eps)
+    or ``softmax`` over each row, or ``act`` - an elementwise activation the dense / head epilogues
+    do not carry (``ROW_ACTS`` of ops/kernels.py; parameters ``p0`` / ``p1``; a per-column PRelu
+    slope in ``gamma_np``), or a Relu / Sigmoid / Tanh that has no dense layer to fold into."""
+    op: str      # layernorm | softmax | act
+    width: int
+    act: str = "none"
+    p0: float = 0.0
+    p1: float = 0.0
+    eps: float = 1e-5
+    gamma_np: Optional[np.ndarray] = None
+    beta_np: Optional[np.ndarray] = None
+    gamma: Any = None
+    beta: Any = None
+    kind: str = "row"
+    src: Optional[int] = None
+
+    @property
+    def out_width(self) -> int:
+        return self.width
 
 
 def step_inputs(steps, i: int) -> Tuple[int, ...]:
@@ -311,8 +345,13 @@ class _Val:
     bidir_pending: bool = False  # a layout-0 bidirectional Y_h still in [D, N, H] order
 
 
-ALIAS_OPS = ("Identity", "Flatten", "Squeeze", "Unsqueeze", "Reshape", "ZipMap", "Cast")
+ALIAS_OPS = ("Identity", "Flatten", "Squeeze", "Unsqueeze", "Reshape", "ZipMap", "Cast", "Dropout")
 ACT_OPS = ("Relu", "Sigmoid", "Tanh")
+# activations that always run as a RowStep: op -> (row act, (attribute, ONNX default) of p0 / p1)
+ROW_ACT_OPS = {"LeakyRelu": ("leaky_relu", ("alpha", 0.01), None), "Elu": ("elu", ("alpha", 1.0), None),
+               "Selu": ("selu", ("alpha", 1.67326319217681884765625), ("gamma", 1.05070102214813232421875)),
+               "Softplus": ("softplus", None, None), "HardSigmoid": ("hard_sigmoid", ("alpha", 0.2), ("beta", 0.5)),
+               "Gelu": ("gelu", None, None)}
 LINEAR_POST = {"NONE": "none", "LOGISTIC": "sigmoid"}
 
 
@@ -390,6 +429,10 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
     def single_use(name):
         return uses.get(root(name), 0) == 1
 
+    # every name a live node (or the output) reads, unaliased: a node's secondary outputs
+    # (a Dropout mask, LayerNormalization's Mean / InvStdDev) are refused when they are in here
+    reads = {i for n in order for i in n["inputs"] if i} | {output_name}
+
     steps: List[Any] = []
     vals: Dict[str, _Val] = {input_name: _Val(-1, in_width)}
 
@@ -465,6 +508,14 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
                 w = len(x)
         vals[out] = replace(v, width=w, scale=s0 * sc, shift=t0 * sc + sh,
                             exclusive=v.exclusive and single_use(name))
+
+    def row_act(name, out, what, act, p0=0.0, p1=0.0, gamma=None):
+        """An elementwise activation as a step of its own (rowops.hip) on ``name``'s plain value."""
+        v = plain(name, what)
+        if v.width <= 0:
+            raise PlanError(f"{what}: the width of its input must be known")
+        i = emit(RowStep("act", v.width, act=act, p0=float(p0), p1=float(p1), gamma_np=gamma), v.step)
+        vals[out] = _Val(i, v.width, ml_col=v.ml_col, cpu_col=v.cpu_col)
 
     for n in order:
         op, a = n["op_type"], n["attrs"]
@@ -582,6 +633,21 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
                 acc = _Val(idx, acc.width + vb.width)
             vals[n["outputs"][0]] = acc
             continue
+        if op == "Clip":
+            lo, hi = -np.inf, np.inf
+            for k, key in ((1, "min"), (2, "max")):
+                if len(ins) > k and ins[k]:
+                    if ins[k] not in inits:
+                        raise PlanError(f"Clip: {key} must be a constant (an attribute or an initializer)")
+                    c = float(np.asarray(const(ins[k]), np.float64).ravel()[0])
+                    lo, hi = (c, hi) if k == 1 else (lo, c)
+            lo, hi = float(a.get("min", lo)), float(a.get("max", hi))
+            if lo == 0.0 and hi == np.inf:
+                op = "Relu"   # clamp(min=0): folds like a Relu below
+            else:
+                f32 = float(np.finfo(np.float32).max)
+                row_act(x, n["outputs"][0], op, "clip", max(lo, -f32), min(hi, f32))
+                continue
         if op in ACT_OPS:
             v = plain(x, op)
             st = steps[v.step] if v.step >= 0 else None
@@ -590,14 +656,89 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
             elif (st is not None and st.kind == "tree" and op == "Sigmoid" and st.post == 0 and st.binary_class < 0
                   and v.exclusive and single_use(x)):
                 st.post = 1
-            else:
-                raise PlanError(f"standalone {op} is not lowered")
+            else:   # after a join, a tree, another activation, or on a value with other readers
+                row_act(x, n["outputs"][0], op, op.lower())
+                continue
             vals[n["outputs"][0]] = replace(v)
+            continue
+        if op in ROW_ACT_OPS:
+            act, k0, k1 = ROW_ACT_OPS[op]
+            if op == "Gelu":
+                approx = str(a.get("approximate", "none"))
+                if approx not in ("none", "tanh"):
+                    raise PlanError(f"Gelu: approximate {approx!r} is not lowered")
+                act = "gelu_tanh" if approx == "tanh" else "gelu"
+            row_act(x, n["outputs"][0], op, act, float(a.get(*k0)) if k0 else 0.0, float(a.get(*k1)) if k1 else 0.0)
+            continue
+        if op == "PRelu":
+            if len(ins) < 2 or ins[1] not in inits:
+                raise PlanError("PRelu: the slope must be a constant (an initializer)")
+            slope = np.asarray(const(ins[1]), np.float32).ravel()
+            w = get(x, op).width
+            if slope.size == 1:
+                row_act(x, n["outputs"][0], op, "prelu", float(slope[0]))
+            elif slope.size == w:
+                row_act(x, n["outputs"][0], op, "prelu", gamma=slope)
+            else:
+                raise PlanError(f"PRelu: {slope.size} slopes for width {w} (one, or one per column)")
+            continue
+        if op == "BatchNormalization":
+            if int(a.get("training_mode", 0)):
+                raise PlanError("BatchNormalization: training_mode=1 is not lowered (inference only)")
+            if len(ins) < 5 or any(i not in inits for i in ins[1:5]):
+                raise PlanError("BatchNormalization: scale, B, mean and var must be initializers")
+            if any(o and o in reads for o in n["outputs"][1:]):
+                raise PlanError("BatchNormalization: the running statistics outputs are not lowered")
+            g_, b_, mu, var = (np.asarray(const(i), np.float64).ravel() for i in ins[1:5])
+            sc = g_ / np.sqrt(var + float(a.get("epsilon", 1e-5)))
+            affine(x, n["outputs"][0], op, scale=sc, shift=b_ - mu * sc)
+            continue
+        if op == "LayerNormalization":
+            if int(a.get("axis", -1)) not in (-1, 1):
+                raise PlanError(f"LayerNormalization: axis {int(a.get('axis', -1))} is not lowered (last axis only)")
+            if any(o and o in reads for o in n["outputs"][1:]):
+                raise PlanError("LayerNormalization: the Mean / InvStdDev outputs are not lowered")
+            if len(ins) < 2 or ins[1] not in inits or (len(ins) > 2 and ins[2] and ins[2] not in inits):
+                raise PlanError("LayerNormalization: Scale (required) and B must be initializers")
+            v = plain(x, op)
+            gam = np.asarray(const(ins[1]), np.float32).ravel()
+            bet = np.asarray(const(ins[2]), np.float32).ravel() if len(ins) > 2 and ins[2] else None
+            if v.width <= 0 or gam.size != v.width or (bet is not None and bet.size != v.width):
+                raise PlanError(f"LayerNormalization: Scale / B do not match the width {v.width}")
+            idx = emit(RowStep("layernorm", v.width, eps=float(a.get("epsilon", 1e-5)), gamma_np=gam, beta_np=bet),
+                       v.step)
+            vals[n["outputs"][0]] = _Val(idx, v.width)
+            continue
+        if op == "Softmax":
+            if int(a.get("axis", -1)) not in (-1, 1):
+                raise PlanError(f"Softmax: axis {int(a.get('axis', -1))} is not lowered (the feature axis only)")
+            v = plain(x, op)
+            st = steps[v.step] if v.step >= 0 else None
+            if (st is not None and st.kind == "dense" and st.act == "none" and st.n == 2 and v.exclusive
+                    and single_use(x)):
+                # softmax over two logits: p1 = sigmoid(z1 - z0), one column (as LinearClassifier SOFTMAX)
+                w64 = st.w_np.astype(np.float64)
+                b64 = np.zeros(2) if st.b_np is None else st.b_np.astype(np.float64)
+                st.w_np = np.ascontiguousarray(w64[1:] - w64[:1], np.float32)
+                st.b_np = (b64[1:] - b64[:1]).astype(np.float32)
+                st.n, st.act = 1, "sigmoid"
+                vals[n["outputs"][0]] = _Val(v.step, 1, ml_col=0, cpu_col=1, narrowed=True)
+                continue
+            if v.width <= 0:
+                raise PlanError("Softmax: the width of its input must be known")
+            idx = emit(RowStep("softmax", v.width), v.step)
+            col = 1 if v.width == 2 else 0
+            vals[n["outputs"][0]] = _Val(idx, v.width, ml_col=col, cpu_col=col)
             continue
         if op in ALIAS_OPS:
             if x not in vals:
                 raise PlanError(f"{op}: value {x!r} is not computed by a lowered node")
             v = vals[x]
+            if op == "Dropout":
+                if len(n["outputs"]) > 1 and n["outputs"][1] and n["outputs"][1] in reads:
+                    raise PlanError("Dropout: its mask output is read, which is not lowered")
+                if len(ins) > 2 and ins[2] in inits and np.asarray(const(ins[2])).ravel()[:1].any():
+                    raise PlanError("Dropout: training_mode is a constant true (inference only)")
             if op == "Reshape" and v.bidir_pending:
                 raise PlanError(f"bidirectional {steps[v.step].kind.upper()}: Y_h [2, N, H] must be transposed to "
                                 "[N, 2, H] before reshaping")
@@ -773,6 +914,10 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
         fv = plain(output_name, "output")
     if not steps or fv.step != len(steps) - 1:
         raise PlanError("the output must be computed by the last lowered step")
+    if has_sequence(steps) and any(s.kind == "row" for s in steps):
+        s = next(s for s in steps if s.kind == "row")
+        raise PlanError(f"sequence models are lowered as chains (GRU / LSTM layers + head) only: a row step "
+                        f"({s.act if s.op == 'act' else s.op}) in a sequence plan is not lowered")
     if has_sequence(steps) and any(s.kind == "join" or s.src != i - 1 for i, s in enumerate(steps)):
         raise PlanError("sequence models are lowered as chains (GRU / LSTM layers + head) only")
     fam = model.metadata.get("family", "")
@@ -927,6 +1072,9 @@ def to_device(plan: Plan, device, precision: str = "fp32") -> Plan:
             s.w1 = (_f32_padded(s.w1_np, k_mult=32) if precision == "fp32" else pad(s.w1_np)).to(device)
             s.b1 = None if s.b1_np is None else torch.from_numpy(np.ascontiguousarray(s.b1_np)).to(device)
             s.w2 = torch.from_numpy(s.w2_np).to(device)
+        elif s.kind == "row":
+            s.gamma, s.beta = (None if t is None else torch.from_numpy(np.ascontiguousarray(t, np.float32)).to(device)
+                               for t in (s.gamma_np, s.beta_np))
     return plan
 
 

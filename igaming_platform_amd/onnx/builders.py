@@ -343,8 +343,88 @@ def residual_mlp(n_features: int = 32, width: int = 128, blocks: int = 2, seed: 
                  [value_info("output", S.FLOAT, ["N", 1])], inits, name="residual_mlp", metadata={"family": "mlp"})
 
 
+def _torch_linear(rng, k: int, n: int, name: str, gain: float = 2.0):
+    """torch.nn.Linear as the exporter writes it: Gemm(transB=1) on a [out, in] weight."""
+    return [tensor(f"W{name}", (rng.standard_normal((n, k)) * np.sqrt(gain / k)).astype(np.float32)),
+            tensor(f"B{name}", (rng.standard_normal(n) * 0.01).astype(np.float32))]
+
+
+def _batch_norm(rng, width: int, x: str, y: str, name: str):
+    """nn.BatchNorm1d in eval mode: per-column scale / B and running mean / var initializers."""
+    inits = [tensor(f"bn{name}_s", rng.uniform(0.5, 1.5, width).astype(np.float32)),
+             tensor(f"bn{name}_b", (rng.standard_normal(width) * 0.1).astype(np.float32)),
+             tensor(f"bn{name}_m", (rng.standard_normal(width) * 0.2).astype(np.float32)),
+             tensor(f"bn{name}_v", rng.uniform(0.5, 2.0, width).astype(np.float32))]
+    return node("BatchNormalization", [x] + [t.name for t in inits], [y], epsilon=1e-5), inits
+
+
+def _layer_norm(rng, width: int, x: str, y: str, name: str):
+    inits = [tensor(f"ln{name}_s", rng.uniform(0.5, 1.5, width).astype(np.float32)),
+             tensor(f"ln{name}_b", (rng.standard_normal(width) * 0.1).astype(np.float32))]
+    return node("LayerNormalization", [x] + [t.name for t in inits], [y], axis=-1, epsilon=1e-5), inits
+
+
+def torch_mlp(n_features: int = 32, hidden: int = 64, layers: int = 2, act: str = "Relu", out: int = 2,
+              seed: int = 12):
+    """An MLP as torch.onnx exports it: (Gemm -> BatchNormalization -> ``act`` -> Dropout) x
+    ``layers``, then Gemm(.., 2) -> Softmax (``out`` 2) or Gemm(.., 1) -> Sigmoid (``out`` 1).
+    ``act`` is the ONNX op: Relu, Sigmoid, Tanh, LeakyRelu, Elu, Selu, Softplus, HardSigmoid, Gelu
+    or PRelu (one slope per column)."""
+    if out not in (1, 2):
+        raise ValueError("out: 1 (Sigmoid) or 2 (Softmax)")
+    rng = np.random.default_rng(seed)
+    nodes, inits = [], [tensor("ratio", np.array(0.1, np.float32))]
+    prev, cur = n_features, "input"
+    for i in range(layers):
+        inits += _torch_linear(rng, prev, hidden, str(i))
+        bn, bn_inits = _batch_norm(rng, hidden, f"z{i}", f"n{i}", str(i))
+        inits += bn_inits
+        a_in = [f"n{i}"]
+        if act == "PRelu":
+            inits.append(tensor(f"slope{i}", rng.uniform(0.05, 0.3, hidden).astype(np.float32)))
+            a_in.append(f"slope{i}")
+        nodes += [node("Gemm", [cur, f"W{i}", f"B{i}"], [f"z{i}"], transB=1), bn, node(act, a_in, [f"a{i}"]),
+                  node("Dropout", [f"a{i}", "ratio"], [f"d{i}"])]
+        prev, cur = hidden, f"d{i}"
+    inits += _torch_linear(rng, prev, out, "o", gain=1.0)
+    nodes += [node("Gemm", [cur, "Wo", "Bo"], ["logits"], transB=1),
+              node("Softmax", ["logits"], ["output"], axis=1) if out == 2 else node("Sigmoid", ["logits"], ["output"])]
+    return model(nodes, [value_info("input", S.FLOAT, ["N", n_features])],
+                 [value_info("output", S.FLOAT, ["N", out])], inits, name="torch_mlp",
+                 metadata={"family": "mlp", "layers": str(layers), "act": act})
+
+
+def tabular_resnet(n_features: int = 32, width: int = 128, blocks: int = 2, norm: str = "layer", seed: int = 13):
+    """The ResNet-style tabular MLP: Gemm; per block norm -> Gemm -> Relu -> Dropout -> Gemm ->
+    Dropout -> Add(skip) -> Relu; then norm -> Relu -> Gemm -> Sigmoid. ``norm``: layer
+    (LayerNormalization) or batch (BatchNormalization)."""
+    if norm not in ("layer", "batch"):
+        raise ValueError("norm: layer or batch")
+    rng = np.random.default_rng(seed)
+    mk = _layer_norm if norm == "layer" else _batch_norm
+    inits = _torch_linear(rng, n_features, width, "in")
+    nodes = [node("Gemm", ["input", "Win", "Bin"], ["h0"], transB=1)]
+    h = "h0"
+    for i in range(blocks):
+        nrm, n_inits = mk(rng, width, h, f"n{i}", str(i))
+        inits += n_inits + _torch_linear(rng, width, width, f"{i}_1") + _torch_linear(rng, width, width, f"{i}_2", 1.0)
+        nodes += [nrm, node("Gemm", [f"n{i}", f"W{i}_1", f"B{i}_1"], [f"z{i}_1"], transB=1),
+                  node("Relu", [f"z{i}_1"], [f"a{i}_1"]), node("Dropout", [f"a{i}_1"], [f"d{i}_1"]),
+                  node("Gemm", [f"d{i}_1", f"W{i}_2", f"B{i}_2"], [f"z{i}_2"], transB=1),
+                  node("Dropout", [f"z{i}_2"], [f"d{i}_2"]),
+                  node("Add", [h, f"d{i}_2"], [f"s{i}"]), node("Relu", [f"s{i}"], [f"h{i + 1}"])]
+        h = f"h{i + 1}"
+    nrm, n_inits = mk(rng, width, h, "nf", "f")
+    inits += n_inits + _torch_linear(rng, width, 1, "o", 1.0)
+    nodes += [nrm, node("Relu", ["nf"], ["af"]), node("Gemm", ["af", "Wo", "Bo"], ["logit"], transB=1),
+              node("Sigmoid", ["logit"], ["output"])]
+    return model(nodes, [value_info("input", S.FLOAT, ["N", n_features])],
+                 [value_info("output", S.FLOAT, ["N", 1])], inits, name="tabular_resnet",
+                 metadata={"family": "mlp", "blocks": str(blocks), "norm": norm})
+
+
 BUILDERS = {"logistic": logistic, "gbdt": gbdt, "stacked": stacked, "ltv_mlp": ltv_mlp, "gru": gru,
-            "lstm": lstm,
+            "lstm": lstm, "torch_mlp": torch_mlp, "tabular_resnet": tabular_resnet,
             "sklearn_linear": sklearn_linear, "linear_regressor": linear_regressor,
             "mlp_classifier": mlp_classifier, "wide_deep": wide_deep, "residual_mlp": residual_mlp}
 

@@ -369,6 +369,46 @@ def join(op: str, A: torch.Tensor, B: torch.Tensor, Y: torch.Tensor, M: int, na:
     _mod().join(d, _stream())
 
 
+ROW_OPS = {"layernorm": 0, "softmax": 1, "act": 2}
+ROW_ACTS = {"relu": 1, "sigmoid": 2, "tanh": 3, "leaky_relu": 4, "elu": 5, "selu": 6, "softplus": 7,
+            "hard_sigmoid": 8, "gelu": 9, "gelu_tanh": 10, "clip": 11, "prelu": 12}
+
+
+def row_op(op: str, X: torch.Tensor, Y: torch.Tensor, M: int, N: int, act: str = "none", p0: float = 0.0,
+           p1: float = 0.0, eps: float = 1e-5, gamma: Optional[torch.Tensor] = None,
+           beta: Optional[torch.Tensor] = None, m_ptr: Optional[torch.Tensor] = None) -> None:
+    """Row op (rowops.hip) on Y[:M, :N] from X[:M, :N]: ``layernorm`` (gamma [N], optional beta
+    [N], eps), ``softmax`` over each row, or ``act`` - one of :data:`ROW_ACTS` with its parameters
+    ``p0`` / ``p1`` (alpha; selu alpha, gamma; hard_sigmoid alpha, beta; clip lo, hi); ``prelu``
+    takes one slope ``p0`` or one per column in ``gamma``."""
+    dev = Y.device
+    for t, name in ((X, "X"), (Y, "Y")):
+        if t.dim() != 2 or t.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"row_op: {name} must be 2-D float32 or bfloat16")
+    if op not in ROW_OPS:
+        raise ValueError(f"row_op: op must be one of {sorted(ROW_OPS)}")
+    if op == "act" and act not in ROW_ACTS:
+        raise ValueError(f"row_op: act must be one of {sorted(ROW_ACTS)}")
+    if N < 1 or M < 0 or X.shape[1] < N or Y.shape[1] < N or min(X.shape[0], Y.shape[0]) < M:
+        raise ValueError("row_op: operand shapes smaller than M / N")
+    if op == "layernorm" and gamma is None:
+        raise ValueError("row_op: layernorm needs gamma")
+    if op == "layernorm" and not eps >= 0:
+        raise ValueError("row_op: eps must be >= 0")
+    if gamma is not None and not (op == "layernorm" or (op == "act" and act == "prelu")):
+        raise ValueError("row_op: gamma is read by layernorm and prelu only")
+    if beta is not None and op != "layernorm":
+        raise ValueError("row_op: beta is read by layernorm only")
+    d = dict(X=_need(X, "X", device=dev), Y=_need(Y, "Y", device=dev),
+             gamma=_opt(gamma, "gamma", dtype=torch.float32, min_numel=N, device=dev),
+             beta=_opt(beta, "beta", dtype=torch.float32, min_numel=N, device=dev),
+             m_ptr=_opt(m_ptr, "m_ptr", dtype=torch.int32), M=int(M), N=int(N), ldx=int(X.shape[1]),
+             ldy=int(Y.shape[1]), x_bf16=int(X.dtype == torch.bfloat16), y_bf16=int(Y.dtype == torch.bfloat16),
+             op=ROW_OPS[op], act=ROW_ACTS.get(act, 0) if op == "act" else 0, p0=float(p0), p1=float(p1),
+             eps=float(eps))
+    _mod().row_op(d, _stream())
+
+
 def mlp_head(hs, X: Optional[torch.Tensor], Y: torch.Tensor, M: int, m_ptr: Optional[torch.Tensor] = None,
              tree_partial=None, trace: Optional[torch.Tensor] = None, ens: Optional[dict] = None) -> None:
     """``hs``: models.plan.HeadStep. Y[:M, 0] = act2(act1(X W1^T + b1) . w2 + b2).

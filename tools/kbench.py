@@ -11,9 +11,51 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def rowops(rounds: int, out: str) -> None:
+    """Device time of every row op (rowops.hip) and of the join add at [8192, 256] and [8192, 2],
+    f32, interleaved rounds in one process (``--config rowops``)."""
+    import torch
+    from igaming_platform_amd.native import hipk
+    from igaming_platform_amd.ops import kernels as K
+    dev = torch.device("cuda", 0)
+    M = 8192
+    ops = {}
+    for N in (256, 2):
+        g = torch.Generator(device="cpu").manual_seed(N)
+        X = torch.randn((M, N), generator=g).to(dev)
+        X2 = torch.randn((M, N), generator=g).to(dev)
+        Y = torch.zeros((M, N), device=dev)
+        gam, bet = torch.rand(N, generator=g).to(dev) + 0.5, torch.randn(N, generator=g).to(dev)
+        ops[f"join_add[{M},{N}]"] = lambda X=X, X2=X2, Y=Y, N=N: K.join("add", X, X2, Y, M, N, N)
+        ops[f"layernorm[{M},{N}]"] = lambda X=X, Y=Y, N=N, gam=gam, bet=bet: K.row_op("layernorm", X, Y, M, N,
+                                                                                      gamma=gam, beta=bet)
+        ops[f"softmax[{M},{N}]"] = lambda X=X, Y=Y, N=N: K.row_op("softmax", X, Y, M, N)
+        for act in K.ROW_ACTS:
+            p0, p1 = {"clip": (-1.0, 1.0), "selu": (1.6732632, 1.050701), "hard_sigmoid": (0.2, 0.5)}.get(act, (0.1, 0.0))
+            ops[f"{act}[{M},{N}]"] = lambda X=X, Y=Y, N=N, act=act, p0=p0, p1=p1: K.row_op("act", X, Y, M, N, act=act,
+                                                                                           p0=p0, p1=p1)
+    times = {k: [] for k in ops}
+    for _ in range(rounds):
+        for k, f in ops.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            hipk().stall(torch.cuda.current_stream().cuda_stream, 300.0)  # device time only, as in main()
+            e0.record()
+            f()
+            e1.record()
+            e1.synchronize()
+            times[k].append(e0.elapsed_time(e1) * 1e3)
+    res = {k: dict(median_us=float(np.median(v[min(5, len(v) - 1):])), min_us=float(np.min(v[min(5, len(v) - 1):])))
+           for k, v in times.items()}
+    for k, v in res.items():
+        print(f"{k:28s} median {v['median_us']:8.1f} us   min {v['min_us']:8.1f} us")
+    if out:
+        with open(out, "w") as f:
+            json.dump(dict(config="rowops", kernels=res), f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", default="cfg3")
+    ap.add_argument("--config", default="cfg3", help="a bench config, or rowops (the row-op kernels alone)")
     ap.add_argument("--batch", type=int, default=0)
     ap.add_argument("--accounts", type=int, default=1 << 20)
     ap.add_argument("--rounds", type=int, default=50)
@@ -23,6 +65,8 @@ def main():
     ap.add_argument("--cold", action="store_true",
                     help="rotating K1 batches draw fresh uniform account slots each round (cold state)")
     a = ap.parse_args()
+    if a.config == "rowops":
+        return rowops(a.rounds, a.out)
     import torch
     from igaming_platform_amd.ops import kernels as K
     from igaming_platform_amd.utils import benchkit
