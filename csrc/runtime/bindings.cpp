@@ -650,7 +650,8 @@ PYBIND11_MODULE(_native, m) {
   py::class_<CpuDevice, std::shared_ptr<CpuDevice>>(m, "CpuDevice")
       .def(py::init<std::shared_ptr<CpuScorer>, int, int>(), py::arg("scorer"), py::arg("depth") = 2,
            py::arg("cap") = 8192, py::keep_alive<1, 2>())
-      .def("device_ops", [](const CpuDevice& d) { return reinterpret_cast<uintptr_t>(d.ops()); });
+      .def("device_ops", [](const CpuDevice& d) { return reinterpret_cast<uintptr_t>(d.ops()); })
+      .def("debug_fail_steps", &CpuDevice::debug_fail_steps, py::arg("n"), py::arg("after") = 0);
 
   py::class_<ShmXchgDevice, std::shared_ptr<ShmXchgDevice>>(m, "ShmXchgDevice")
       .def(py::init<std::shared_ptr<CpuScorer>, const std::string&, int, int, int, int, bool, double>(),
@@ -836,8 +837,15 @@ PYBIND11_MODULE(_native, m) {
           py::gil_scoped_release rel;
           out = s.core->score_batch_view(p, size_t(n), now, t0_ns);
         }
-        // allocate the result object under the GIL, fill it without: the MB-sized copy of a
-        // batch response would otherwise serialise every ingress thread on the GIL
+        // The response is serialised into the thread's resident scratch buffer and copied once
+        // into a bytes object of exactly its size (allocated under the GIL, filled without: the
+        // MB-sized copy would otherwise serialise every ingress thread on the GIL). Letting the
+        // core write into the bytes object itself (ServeCore::score_batch_into), allocated at
+        // the response's upper bound or at a typical size and shrunk with _PyBytes_Resize, was
+        // measured and is slower: glibc sets its mmap threshold from the SHRUNK size of the
+        // block it frees, so the next, larger allocation is mmap'd afresh and pays a page fault
+        // per 4 KB written on every call (299 per 1.2 MB response against 0 for an exact-size
+        // allocation; profiles/NOTES.md round 9)
         PyObject* b = PyBytes_FromStringAndSize(nullptr, py::ssize_t(out.size()));
         if (!b) throw py::error_already_set();
         {

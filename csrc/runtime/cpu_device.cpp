@@ -49,6 +49,10 @@ int32_t CpuDevice::submit_fn(void* ctx, int32_t slot, int32_t n, int32_t, int64_
                              int32_t errlen) {
   auto* d = static_cast<CpuDevice*>(ctx);
   Slot& s = d->slots_[slot];
+  if (d->fail_steps_.load() > 0 && d->pass_steps_.fetch_sub(1) <= 0 && d->fail_steps_.fetch_sub(1) > 0) {
+    set_err(err, errlen, "CpuDevice: injected step failure");
+    return -1;
+  }
   try {
     s.wf = (wf & IGP_SUBMIT_WANT_FEATURES) != 0;  // (IGP_SUBMIT_NO_UPDATE: nothing to skip here)
     d->sc_->score(s.rows.data(), size_t(n), now, true, s.res.data(), s.wf ? s.feat.data() : nullptr);

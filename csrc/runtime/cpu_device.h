@@ -26,6 +26,12 @@ class CpuDevice {
  public:
   CpuDevice(std::shared_ptr<CpuScorer> sc, int depth, int cap);
   const IgpDeviceOps* ops() const { return &ops_; }
+  // fault injection (tests): after `after` more steps, the next `n` steps fail in submit,
+  // scoring nothing
+  void debug_fail_steps(int n, int after) {
+    pass_steps_.store(after);
+    fail_steps_.store(n);
+  }
 
  private:
   struct Slot {
@@ -41,6 +47,7 @@ class CpuDevice {
   static const void* features_fn(void* ctx, int32_t slot);
   std::shared_ptr<CpuScorer> sc_;
   std::vector<Slot> slots_;
+  std::atomic<int> fail_steps_{0}, pass_steps_{0};
   IgpDeviceOps ops_{};
 };
 

@@ -57,6 +57,12 @@ struct ServeCore::Item {
   ResultRec res1{};             // unary storage
   FeatRec feat1{};
   uint64_t tag = 0;
+  // streamed batch item (direct device): its segments are serialised from the slot buffers, in
+  // row order, at out_cur (the caller thread only)
+  bool stream = false;
+  char* out_cur = nullptr;
+  size_t ser_rows = 0;          // rows serialised so far == item_pos of the next segment
+  int64_t ser_ns = 0;
   int64_t t0 = 0, t_enq = 0;
   int64_t t_issue = 0;          // the first step holding rows of this item was formed (q_mu_)
   int32_t seq_first = 0, seq_last = 0;  // batch sequence numbers of its first / last step (q_mu_)
@@ -232,15 +238,46 @@ void ServeCore::wait_item(Item* it) {
       if (st->failed) {
         it->failed = true;
         if (it->err.empty()) it->err = st->err;
-      } else {
+      } else if (!it->stream) {
         finish_seg(*st, seg);
+      } else if (!it->failed) {  // (a failed item's response is never handed out)
+        stream_seg(*st, seg);
       }
       done += size_t(seg.count);
-      release_step_ref(st);
+      release_step_ref(st);  // only now: the segment was read from the slot's buffers
     }
-    a_copy_.fetch_add(now_ns() - t, std::memory_order_relaxed);
+    const int64_t dt = now_ns() - t;
+    if (it->stream) {  // serialisation, not a copy
+      it->ser_ns += dt;
+      a_serialize_.fetch_add(dt, std::memory_order_relaxed);
+    } else {
+      a_copy_.fetch_add(dt, std::memory_order_relaxed);
+    }
     l.lock();
   }
+}
+
+// One ready segment of a streamed batch item: its rows' ScoreBatchResponse entries written
+// straight from the slot's result / feature buffers behind the previous segment's. Segments
+// arrive in row order by construction - issue_step takes an item's rows front to back and
+// completion_loop hands steps on in submit order - and that is checked, not assumed: a
+// segment out of order fails the item.
+void ServeCore::stream_seg(const Step& st, const Seg& s) {
+  Item* it = s.item;
+  if (size_t(s.item_pos) != it->ser_rows) {
+    it->failed = true;
+    if (it->err.empty())
+      it->err = "segment out of row order: rows from " + std::to_string(s.item_pos) + " after " +
+                std::to_string(it->ser_rows) + " serialised";
+    return;
+  }
+  const ResultRec* r = static_cast<const ResultRec*>(dev_->results(dev_->ctx, st.slot)) + s.dev_pos;
+  const FeatRec* f = it->wf ? static_cast<const FeatRec*>(dev_->features(dev_->ctx, st.slot)) : nullptr;
+  it->out_cur = wire::write_batch_rows(it->out_cur, r, f ? f + s.dev_pos : nullptr, (now_ns() - it->t0) / 1000000,
+                                       size_t(s.count));
+  it->ser_rows += size_t(s.count);
+  record_decisions(r, s.count);
+  audit_seg(r, it->rows.data() + s.item_pos, 0, s.count);
 }
 
 std::string ServeCore::score_batch(const char* data, size_t n, int64_t now, int64_t t0_ns) {
@@ -249,13 +286,13 @@ std::string ServeCore::score_batch(const char* data, size_t n, int64_t now, int6
 }
 
 std::string_view ServeCore::score_batch_view(const char* data, size_t n, int64_t now, int64_t t0_ns) {
+  char* buf = nullptr;
+  const size_t len = score_batch_into(data, n, now, t0_ns, [&](size_t ub) { return buf = wire::response_scratch(ub); });
+  return len ? std::string_view(buf, len) : std::string_view();
+}
+
+size_t ServeCore::score_batch_into(const char* data, size_t n, int64_t now, int64_t t0_ns, const Alloc& alloc) {
   const int64_t t0 = t0_ns > 0 ? t0_ns : now_ns();
-  thread_local std::vector<wire::TxRow> rows;
-  rows.clear();
-  const int64_t ta = now_ns();
-  wire::parse_batch_rows(data, n, rows);
-  const int64_t tb = now_ns();
-  if (rows.empty()) return {};
   Item it;
   // the item's packed rows reuse this thread's buffer: a fresh 512 KB vector per 8192-row
   // request was an mmap'd allocation, zero-filled and page-faulted every time (~8 % of the
@@ -277,31 +314,53 @@ std::string_view ServeCore::score_batch_view(const char* data, size_t n, int64_t
   it.kind = 0;
   it.now = now >= 0 ? now : wall_s();
   it.wf = opt_.features;
+  it.t0 = t0;
+  thread_local std::vector<wire::TxRow> rows;
+  rows.clear();
+  const int64_t ta = now_ns();
+  wire::parse_batch_rows(data, n, rows);
+  const int64_t tb = now_ns();
+  if (rows.empty()) return 0;
   resolve_rows(rows, &it);
   const int64_t tc = now_ns();
+  char* const out = alloc(it.n * wire::kMaxBatchRowBytes);
+  if (!out) throw std::runtime_error("ServeCore: no response buffer");
   thread_local std::vector<ResultRec> res;
   thread_local std::vector<FeatRec> feat;
-  res.resize(it.n);
-  if (it.wf) feat.resize(it.n);
-  it.res = res.data();
-  it.feat = it.wf ? feat.data() : nullptr;
+  if (!exchange_) {  // the segments are serialised in place, from the slots (wait_item)
+    it.stream = true;
+    it.out_cur = out;
+  } else {  // owner-permuted rows: staged in request order, serialised at the end
+    res.resize(it.n);
+    if (it.wf) feat.resize(it.n);
+    it.res = res.data();
+    it.feat = it.wf ? feat.data() : nullptr;
+  }
   enqueue(&it);
   const int64_t tq = it.t_enq;
   wait_item(&it);
   if (it.failed) throw std::runtime_error("ServeCore: batch failed: " + it.err);
   const int64_t td = now_ns();
-  const std::string_view out = wire::batch_response_scratch(it.res, it.feat, nullptr, (td - t0) / 1000000, it.n);
+  size_t len;
+  int64_t ser = it.ser_ns;
+  if (it.stream) {
+    if (it.ser_rows != it.n) throw std::runtime_error("ServeCore: batch failed: rows missing from the response");
+    len = size_t(it.out_cur - out);
+  } else {
+    len = wire::write_batch_response(out, it.res, it.feat, nullptr, (td - t0) / 1000000, it.n);
+    ser = now_ns() - td;
+    a_serialize_.fetch_add(ser, std::memory_order_relaxed);
+  }
   const int64_t te = now_ns();
   // this call's stage times (last_timings(): per-request tails, not only sums)
   CallTimings& ct = last_timings_tl();
-  ct = CallTimings{tb - ta, tc - tb, it.t_issue - tq, td - it.t_issue, te - td, te - t0, int64_t(it.n), it.seq_first,
-                   it.seq_last};
+  ct = CallTimings{tb - ta, tc - tb, it.t_issue - tq, td - it.t_issue - it.ser_ns, ser, te - t0, int64_t(it.n),
+                   it.seq_first, it.seq_last};
   a_parse_.fetch_add(tb - ta, std::memory_order_relaxed);
   a_resolve_.fetch_add(tc - tb, std::memory_order_relaxed);
-  a_serialize_.fetch_add(te - td, std::memory_order_relaxed);
   a_items_.fetch_add(1, std::memory_order_relaxed);
   a_rows_.fetch_add(int64_t(it.n), std::memory_order_relaxed);
-  return out;
+  return len;
 }
 
 void ServeCore::score_rows(const ReqRec* rows, const int32_t* owners, size_t n, int64_t now, bool want_features,

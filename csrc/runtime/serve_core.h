@@ -9,11 +9,17 @@
 //     per-owner chunk capacity in exchange mode), packs the rows into the slot's pinned
 //     buffer, launches the slot through the device function table (device_ops.h)
 //   completion thread
-//     waits for slots in submit order; batch items copy their own result rows out (in
-//     parallel, on their own threads); unary items are finished (copy + serialise) by a
+//     waits for slots in submit order; unary items are finished (copy + serialise) by a
 //     finisher pool and handed back through a completion queue polled from Python
 //   callers
-//     serialise the ScoreBatchResponse from their result rows
+//     ScoreBatch on a direct (non-exchange) device: each segment of the request is serialised
+//     straight from the slot's pinned result / feature buffers into the response buffer, in row
+//     order, and the slot is released after that (no staging copy). A row's response_time_ms is
+//     therefore the time from the call's t0 to the serialisation of ITS segment: for a request
+//     of one segment that is what it always was, less the serialisation itself; the segments of
+//     a longer request carry the time each of them was answered. Exchange devices and
+//     score_rows copy their (owner-permuted) rows out first and serialise afterwards, all rows
+//     stamped at the end
 //
 // Unary ScoreTransaction calls are ordinary 1-row items in the same FIFO, so concurrent
 // unary calls and batches share device micro-batches (the MPSC micro-batcher of SURVEY 3.6b).
@@ -76,7 +82,8 @@ class StepClock {
 };
 
 // stage times of one ScoreBatch call (ns): parse, resolve, queue (enqueue -> its first device
-// step formed), device (first step formed -> every row back, incl. the copy out), serialize, total
+// step formed), device (first step formed -> every row back, incl. the copy out where rows are
+// still staged; the in-place serialisation of the segments is NOT in it), serialize, total
 struct CallTimings {
   int64_t parse = 0, resolve = 0, queue = 0, device = 0, serialize = 0, total = 0, rows = 0;
   int32_t seq_first = 0, seq_last = 0;  // the batch sequence numbers of the first / last step of its rows
@@ -131,8 +138,15 @@ class ServeCore {
   // ScoreBatch: request bytes -> response bytes (blocking; callable from many threads)
   std::string score_batch(const char* data, size_t n, int64_t now, int64_t t0_ns);
   // the same, the response left in the calling thread's scratch buffer (valid until the
-  // thread's next call): the binding copies it into the Python bytes object without the GIL
+  // thread's next call): the native HTTP/2 server frames it from there
   std::string_view score_batch_view(const char* data, size_t n, int64_t now, int64_t t0_ns);
+  // the same, serialised into a buffer of the caller's: alloc(upper_bound) -> buffer is called
+  // exactly once, after parsing and resolving (not at all for a request without rows), with an
+  // upper bound of the response size for the request's row count; returns the bytes written.
+  // A null buffer fails the call. Nothing is enqueued before alloc returned, and a failed call
+  // leaves no trace in the thread's next response
+  using Alloc = std::function<char*(size_t)>;
+  size_t score_batch_into(const char* data, size_t n, int64_t now, int64_t t0_ns, const Alloc& alloc);
   // pre-resolved rows (REQREC with slots; owners[] per row when world > 1): results in row order
   void score_rows(const ReqRec* rows, const int32_t* owners, size_t n, int64_t now, bool want_features,
                   ResultRec* res, FeatRec* feat);
@@ -224,6 +238,7 @@ class ServeCore {
   bool issue_step(std::unique_lock<std::mutex>& lk, bool allow_empty);
   int next_slot_locked() const;
   void finish_seg(const Step& st, const Seg& s);
+  void stream_seg(const Step& st, const Seg& s);
   void release_step_ref(Step* st);
   void resolve_rows(std::vector<wire::TxRow>& rows, Item* it);
   void converge(int64_t gen);

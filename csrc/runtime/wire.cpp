@@ -367,29 +367,40 @@ size_t write_tx_response(char* out, const ResultRec& r, const FeatRec* f, int64_
   return size_t(write_tx_body(out, r, f, ms) - out);
 }
 
-size_t write_batch_response(char* dst, const ResultRec* r, const FeatRec* f, const int64_t* ms, int64_t ms_all,
-                            size_t n) {
+char* write_batch_rows(char* dst, const ResultRec* r, const FeatRec* f, int64_t ms, size_t n) {
   char* p = dst;
   for (size_t i = 0; i < n; ++i) {
     *p = char(T1(1, pb::LEN));
     char* slot = p + 1;
-    p = close_len(slot, write_tx_body(slot + 1, r[i], f ? f + i : nullptr, ms ? ms[i] : ms_all));
+    p = close_len(slot, write_tx_body(slot + 1, r[i], f ? f + i : nullptr, ms));
   }
+  return p;
+}
+
+size_t write_batch_response(char* dst, const ResultRec* r, const FeatRec* f, const int64_t* ms, int64_t ms_all,
+                            size_t n) {
+  if (!ms) return size_t(write_batch_rows(dst, r, f, ms_all, n) - dst);
+  char* p = dst;
+  for (size_t i = 0; i < n; ++i) p = write_batch_rows(p, r + i, f ? f + i : nullptr, ms[i], 1);
   return size_t(p - dst);
 }
 
-std::string_view batch_response_scratch(const ResultRec* r, const FeatRec* f, const int64_t* ms, int64_t ms_all,
-                                        size_t n) {
-  // worst case per row into an uninitialised, grow-only per-thread buffer (its pages stay
-  // resident across requests: a fresh multi-MB buffer per response pays a page fault per 4 KB)
+char* response_scratch(size_t need) {
+  // an uninitialised, grow-only per-thread buffer (its pages stay resident across requests: a
+  // fresh multi-MB buffer per response pays a page fault per 4 KB)
   thread_local std::unique_ptr<char[]> scratch;
   thread_local size_t scratch_cap = 0;
-  const size_t need = n * kMaxBatchRowBytes;
   if (scratch_cap < need) {
     scratch.reset(new char[need]);
     scratch_cap = need;
   }
-  return std::string_view(scratch.get(), write_batch_response(scratch.get(), r, f, ms, ms_all, n));
+  return scratch.get();
+}
+
+std::string_view batch_response_scratch(const ResultRec* r, const FeatRec* f, const int64_t* ms, int64_t ms_all,
+                                        size_t n) {
+  char* buf = response_scratch(n * kMaxBatchRowBytes);  // worst case per row
+  return std::string_view(buf, write_batch_response(buf, r, f, ms, ms_all, n));
 }
 
 void append_batch_response(std::string& out, const ResultRec* r, const FeatRec* f, const int64_t* ms, int64_t ms_all,

@@ -66,6 +66,12 @@ std::string serialize_feature_vector(const FeatRec& f);
 constexpr size_t kMaxTxResponse = 1024;
 size_t write_tx_response(char* out, const ResultRec& r, const FeatRec* f, int64_t ms);
 constexpr size_t kMaxBatchRowBytes = kMaxTxResponse + 8;
+// n ScoreBatchResponse entries, all stamped response_time_ms = ms, written at dst; returns the
+// end. dst needs n * kMaxBatchRowBytes of room whatever the rows encode to: a device-encoded
+// feature image is copied as its fixed 128 bytes and the pointer advanced by its real length.
+char* write_batch_rows(char* dst, const ResultRec* r, const FeatRec* f, int64_t ms, size_t n);
+// this thread's grow-only response buffer, at least `need` bytes (valid until its next call on the thread)
+char* response_scratch(size_t need);
 // ScoreBatchResponse of n rows written at dst (capacity n * kMaxBatchRowBytes); returns its size
 size_t write_batch_response(char* dst, const ResultRec* r, const FeatRec* f, const int64_t* ms, int64_t ms_all,
                             size_t n);
