@@ -1030,7 +1030,8 @@ def validate_sparse(s: TreeStep) -> None:
     ch = nodes[~leaf][:, 2:4]
     if ((ch < 0) | (ch >= N)).any():
         raise PlanError("sparse trees: child index out of range")
-    if (nodes[~leaf, 0].view(np.uint32) & 0xFFFF).max(initial=0) > s.max_feature:
+    # initial -1: an ensemble of single-leaf trees reads no feature (max_feature = -1)
+    if (nodes[~leaf, 0].view(np.uint32) & 0xFFFF).astype(np.int64).max(initial=-1) > s.max_feature:
         raise PlanError("sparse trees: feature id above max_feature")
     # longest path by level expansion from the roots (bounded by depth + 1 levels)
     frontier = s.roots_np.astype(np.int64)

@@ -227,7 +227,7 @@ def test_head_tree_partial_staging(groups, k, average, with_base, precision):
     assert D.untouched(Y, M, 1)
 
 
-def _stacked(n_trees, hidden):
+def _stacked(n_trees, hidden, poison=False):
     from igaming_platform_amd.engine.runner import DeviceModel
     from igaming_platform_amd.models.plan import compile_onnx, to_device
     from igaming_platform_amd.native import native
@@ -238,6 +238,8 @@ def _stacked(n_trees, hidden):
     plan = to_device(compile_onnx(om), "cuda")
     assert [s.kind for s in plan.steps] == ["tree", "head"]
     dm = DeviceModel(plan, "cuda", [64])
+    if poison:   # a group that stores nothing leaves NaN for the reduction
+        dm.tree_partial.fill_(float("nan"))
     X = np.random.default_rng(6).uniform(0, 1, (64, 128)).astype(np.float32)
     ref = np.asarray(N.Executor(om).run({"input": X})["output"])[:, 0]
     out = dm.run(torch.from_numpy(X).cuda(), 64)
@@ -256,6 +258,24 @@ def test_tree_head_one_launch_at_16_groups(hidden, monkeypatch):
     assert int(dm.tile_cnt.abs().sum()) == 0
     np.testing.assert_allclose(got, ref, atol=1e-5, rtol=0)
     assert np.ptp(ref) > 1e-3
+
+
+def test_tree_head_one_launch_with_an_empty_last_group(monkeypatch):
+    """129 trees in a 64-row bucket: 16 groups of 9, group 14 holds 3 trees and group 15 none; its
+    blocks still store zeros into the (NaN-poisoned) slab and take their tickets. Against the
+    float64 walk of the trees pushed through the float64 head (tests/tree_cases.py)."""
+    from tests import tree_cases as TC
+    monkeypatch.setenv("IGP_TREE_HEAD", "1")
+    monkeypatch.delenv("IGP_TREE_GROUPS", raising=False)
+    dm, plan, got, ref = _stacked(129, 100, poison=True)
+    assert dm.tree_groups[64] == 16 and _K().tree_head_ok(plan.steps[0], plan.steps[1], 16)
+    assert TC.group_sizes(129, 16)[-2:] == [3, -6]
+    assert int(dm.tile_cnt.abs().sum()) == 0
+    trees, head = TC.stacked_parts(129, hidden=100)
+    X = np.random.default_rng(6).uniform(0, 1, (64, 128)).astype(np.float32)
+    np.testing.assert_allclose(got, TC.stacked_ref(trees, head, X), **TOL_HEAD["fp32"])
+    np.testing.assert_allclose(got, ref, atol=1e-5, rtol=0)
+    assert not bool(_t().isnan(dm.tree_partial[:16 * 64 * 32]).any())
 
 
 def test_tree_head_routing_past_16_groups(monkeypatch):
