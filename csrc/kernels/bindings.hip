@@ -507,6 +507,11 @@ PYBIND11_MODULE(_hipk, m) {
     a.ws_trace = ptr<int64_t*>(d, "ws_trace");
     a.split = geti(d, "split");
     a.reverse = geti(d, "reverse", 0);
+    a.masked = geti(d, "masked", 0);
+    a.lens = ptr<const int32_t*>(d, "lens");
+    if (a.lens && (!a.masked || a.mode != 0)) throw std::runtime_error("gru: lens needs masked = 1 and dense input");
+    if (a.masked && (a.T < 1 || a.T > 65535 || a.I < 8))
+      throw std::runtime_error("gru: masked needs 1 <= T <= 65535 and I >= 8");
     if (a.split) {
       for (int l = 0; l < a.n_layers; ++l)
         if (!a.layer[l].W_lo || !a.layer[l].R_lo) throw std::runtime_error("gru: split mode needs residual weights");
@@ -560,6 +565,10 @@ PYBIND11_MODULE(_hipk, m) {
     a.out = ptr<float*>(d, "out");
     a.tile_rows = geti(d, "tile_rows");
     a.reverse = geti(d, "reverse", 0);
+    a.masked = geti(d, "masked", 0);
+    a.lens = ptr<const int32_t*>(d, "lens");
+    if (a.lens && (!a.masked || a.mode != 0)) throw std::runtime_error("lstm: lens needs masked = 1 and dense input");
+    if (a.masked && a.T > 65535) throw std::runtime_error("lstm: masked needs T <= 65535");
     if (a.tile_rows != 0 && a.tile_rows != 16 && a.tile_rows != 32) throw std::runtime_error("lstm: tile_rows 16|32");
     if (a.H != 64 && a.H != 128 && a.H != 256) throw std::runtime_error("lstm: H must be 64, 128 or 256");
     if (a.layer[0].kx_pad != 32 && a.layer[0].kx_pad != 64) throw std::runtime_error("lstm: input dim must pad to 32 or 64");

@@ -14,6 +14,7 @@
 // or a dense [T][B][I] tensor, mode 0).
 #include "common.h"
 #include "launch.h"
+#include "seq_window.h"
 
 namespace igp {
 
@@ -60,10 +61,13 @@ __device__ __forceinline__ bf16x8 lds_frag(const uint16_t* base, int stride, int
 // The recurrence is latency-bound on the streamed weight fragments: tiles are processed in
 // groups of G (G*RT <= 2, so accumulators stay at 32 floats) and every k-step issues the
 // 3*G fragments of the group at once; with the k loop unrolled by 2 ~12 loads are in flight.
-template <int RT, int KSX, int KSH, int LBR, int NW>
+// MASKED: live(rt, r) says whether accumulator row rt*16 + crow + r is inside its window at this
+// step; a dead row keeps hs and carries its bf16 value into hnext.
+template <int RT, int KSX, int KSH, int LBR, int NW, int MASKED = 0>
 __device__ __forceinline__ void layer_step(const WFrag& gW, const WFrag& gR, const float* bias, const uint16_t* in,
                                            int in_stride, const uint16_t* hprev, uint16_t* hnext,
-                                           uint16_t* rb, float (&hs)[KSH * 2 / NW][RT][4], int lane, int wave) {
+                                           uint16_t* rb, float (&hs)[KSH * 2 / NW][RT][4], int lane, int wave,
+                                           const SeqLive<MASKED>& live) {
   constexpr int HT = KSH * 2;      // hidden tiles of 16 units
   constexpr int HTW = HT / NW;     // per wave
   constexpr int G = (RT == 1 && HTW >= 2) ? 2 : 1;
@@ -136,7 +140,8 @@ __device__ __forceinline__ void layer_step(const WFrag& gW, const WFrag& gR, con
           const float rr = sig_(ar[u][rt][r] + br_);
           if constexpr (LBR != 0) {
             const float hh = tanh_(ax[u][rt][r] + bias[2 * H + j] + rr * (ah[u][rt][r] + bias[5 * H + j]));
-            const float h = (1.f - z) * hh + z * hs[i][rt][r];
+            float h = (1.f - z) * hh + z * hs[i][rt][r];
+            if constexpr (MASKED != 0) h = live(rt, r) ? h : hs[i][rt][r];
             hs[i][rt][r] = h;
             hnext[(rt * 16 + crow + r) * HS + j] = f32_to_bf16(h);
           } else {
@@ -181,7 +186,8 @@ __device__ __forceinline__ void layer_step(const WFrag& gW, const WFrag& gR, con
           for (int r = 0; r < 4; ++r) {
             const float hh = tanh_(xk[i][rt][r] + bxh + ah[u][rt][r] + bhh);
             const float z = zk[i][rt][r];
-            const float h = (1.f - z) * hh + z * hs[i][rt][r];
+            float h = (1.f - z) * hh + z * hs[i][rt][r];
+            if constexpr (MASKED != 0) h = live(rt, r) ? h : hs[i][rt][r];
             hs[i][rt][r] = h;
             hnext[(rt * 16 + crow + r) * HS + j] = f32_to_bf16(h);
           }
@@ -208,12 +214,13 @@ __device__ __forceinline__ void gru_split(float x, uint16_t& hi, uint16_t& lo) {
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, acc, 0, 0, 0);   \
   } while (0)
 
-template <int RT, int KSX, int KSH, int LBR, int NW>
+template <int RT, int KSX, int KSH, int LBR, int NW, int MASKED = 0>
 __device__ __forceinline__ void layer_step_x3(const WFrag& gW, const WFrag& gWl, const WFrag& gR, const WFrag& gRl,
                                               const float* bias, const uint16_t* in, const uint16_t* inl, int in_stride,
                                               const uint16_t* hprev, const uint16_t* hprevl, uint16_t* hnext,
                                               uint16_t* hnextl, uint16_t* rb, uint16_t* rbl,
-                                              float (&hs)[KSH * 2 / NW][RT][4], int lane, int wave) {
+                                              float (&hs)[KSH * 2 / NW][RT][4], int lane, int wave,
+                                              const SeqLive<MASKED>& live) {
   constexpr int HT = KSH * 2;
   constexpr int HTW = HT / NW;
   constexpr int H = KSH * 32;
@@ -272,7 +279,8 @@ __device__ __forceinline__ void layer_step_x3(const WFrag& gW, const WFrag& gWl,
         const int o = (rt * 16 + crow + r) * HS + j;
         if constexpr (LBR != 0) {
           const float hh = tanh_(ax[rt][r] + bias[2 * H + j] + rr * (ah[rt][r] + bias[5 * H + j]));
-          const float h = (1.f - z) * hh + z * hs[i][rt][r];
+          float h = (1.f - z) * hh + z * hs[i][rt][r];
+          if constexpr (MASKED != 0) h = live(rt, r) ? h : hs[i][rt][r];
           hs[i][rt][r] = h;
           gru_split(h, hnext[o], hnextl[o]);
         } else {
@@ -308,7 +316,8 @@ __device__ __forceinline__ void layer_step_x3(const WFrag& gW, const WFrag& gWl,
         for (int r = 0; r < 4; ++r) {
           const float hh = tanh_(xk[i][rt][r] + bxh + ah[rt][r] + bhh);
           const float z = zk[i][rt][r];
-          const float h = (1.f - z) * hh + z * hs[i][rt][r];
+          float h = (1.f - z) * hh + z * hs[i][rt][r];
+          if constexpr (MASKED != 0) h = live(rt, r) ? h : hs[i][rt][r];
           hs[i][rt][r] = h;
           const int o = (rt * 16 + crow + r) * HS + j;
           gru_split(h, hnext[o], hnextl[o]);
@@ -369,7 +378,11 @@ __device__ __forceinline__ void emit_outputs(const GruArgs& a, float (&hs)[KSH *
   }
 }
 
-template <int RT, int KSX, int KSH, int LBR, int NW>
+// MASKED (every batch-parallel kernel below): per-row sequence lengths. The my_c == 0 stager of
+// each row publishes the row's live window in LDS (wl[M], after red); every step each lane tests
+// the windows of its accumulator rows (SeqLive) and the layer steps hold a row outside its window.
+// Dead steps skip nothing: the barriers stay block-uniform.
+template <int RT, int KSX, int KSH, int LBR, int NW, int MASKED = 0>
 __global__ void __launch_bounds__(NW * 64) gru_kernel(GruArgs a) {
   constexpr int M = RT * 16;
   constexpr int H = KSH * 32;
@@ -444,6 +457,9 @@ __global__ void __launch_bounds__(NW * 64) gru_kernel(GruArgs a) {
     }
     return v;
   };
+  if constexpr (MASKED != 0) {
+    if (stager && my_c == 0) reinterpret_cast<uint32_t*>(red + NW * M)[my_rr] = seq_window(a, grow, n_live, valid_from);
+  }
   __syncthreads();  // zeroing done before the first staged row lands
   if (stager) *reinterpret_cast<uint4*>(XB(0) + my_rr * XS + my_c * 8) = load_x(0);
 
@@ -458,12 +474,16 @@ __global__ void __launch_bounds__(NW * 64) gru_kernel(GruArgs a) {
 
   for (int t = 0; t < a.T; ++t) {
     const int pb = t & 1, nb = pb ^ 1;
+    SeqLive<MASKED> live;
+    if constexpr (MASKED != 0)
+      live = {reinterpret_cast<const uint32_t*>(red + NW * M), (lane >> 4) * 4, a.reverse ? a.T - 1 - t : t};
     const uint4 xn = (t + 1 < a.T) ? load_x(t + 1) : make_uint4(0, 0, 0, 0);
-    layer_step<RT, KSX, KSH, LBR, NW>(w0, r0, bias, XB(pb), XS, HB(0, pb), HB(0, nb), rb, hs0, lane, wave);
+    layer_step<RT, KSX, KSH, LBR, NW, MASKED>(w0, r0, bias, XB(pb), XS, HB(0, pb), HB(0, nb), rb, hs0, lane, wave,
+                                              live);
     __syncthreads();
     if (a.n_layers == 2) {
-      layer_step<RT, KSH, KSH, LBR, NW>(w1, r1, bias + 6 * H, HB(0, nb), HS, HB(1, pb), HB(1, nb), rb, hs1, lane,
-                                        wave);
+      layer_step<RT, KSH, KSH, LBR, NW, MASKED>(w1, r1, bias + 6 * H, HB(0, nb), HS, HB(1, pb), HB(1, nb), rb, hs1,
+                                                lane, wave, live);
     }
     if (stager && t + 1 < a.T) *reinterpret_cast<uint4*>(XB(nb) + my_rr * XS + my_c * 8) = xn;
     __syncthreads();
@@ -481,7 +501,7 @@ __global__ void __launch_bounds__(NW * 64) gru_kernel(GruArgs a) {
 // Batch-parallel recurrence in split mode (layer_step_x3): the same structure as gru_kernel,
 // with every LDS activation tile doubled into hi / lo halves (16 rows per workgroup keeps it
 // within the LDS: ~96 KB at H = 256).
-template <int RT, int KSX, int KSH, int LBR, int NW>
+template <int RT, int KSX, int KSH, int LBR, int NW, int MASKED = 0>
 __global__ void __launch_bounds__(NW * 64) gru_x3_kernel(GruArgs a) {
   constexpr int M = RT * 16;
   constexpr int H = KSH * 32;
@@ -558,6 +578,9 @@ __global__ void __launch_bounds__(NW * 64) gru_x3_kernel(GruArgs a) {
                       l8[6] | (uint32_t)l8[7] << 16);
     }
   };
+  if constexpr (MASKED != 0) {
+    if (stager && my_c == 0) reinterpret_cast<uint32_t*>(red + NW * M)[my_rr] = seq_window(a, grow, n_live, valid_from);
+  }
   __syncthreads();
   if (stager) {
     uint4 h, l;
@@ -576,15 +599,19 @@ __global__ void __launch_bounds__(NW * 64) gru_x3_kernel(GruArgs a) {
 
   for (int t = 0; t < a.T; ++t) {
     const int pb = t & 1, nb = pb ^ 1;
+    SeqLive<MASKED> live;
+    if constexpr (MASKED != 0)
+      live = {reinterpret_cast<const uint32_t*>(red + NW * M), (lane >> 4) * 4, a.reverse ? a.T - 1 - t : t};
     uint4 xh, xl;
     load_x(t + 1, xh, xl);
-    layer_step_x3<RT, KSX, KSH, LBR, NW>(w0, w0l, r0, r0l, bias, XB(0, pb), XB(1, pb), XS, HB(0, 0, pb), HB(1, 0, pb),
-                                         HB(0, 0, nb), HB(1, 0, nb), rb, rb + M * HS, hs0, lane, wave);
+    layer_step_x3<RT, KSX, KSH, LBR, NW, MASKED>(w0, w0l, r0, r0l, bias, XB(0, pb), XB(1, pb), XS, HB(0, 0, pb),
+                                                 HB(1, 0, pb), HB(0, 0, nb), HB(1, 0, nb), rb, rb + M * HS, hs0, lane,
+                                                 wave, live);
     __syncthreads();
     if (a.n_layers == 2) {
-      layer_step_x3<RT, KSH, KSH, LBR, NW>(w1, w1l, r1, r1l, bias + 6 * H, HB(0, 0, nb), HB(1, 0, nb), HS,
-                                           HB(0, 1, pb), HB(1, 1, pb), HB(0, 1, nb), HB(1, 1, nb), rb, rb + M * HS,
-                                           hs1, lane, wave);
+      layer_step_x3<RT, KSH, KSH, LBR, NW, MASKED>(w1, w1l, r1, r1l, bias + 6 * H, HB(0, 0, nb), HB(1, 0, nb), HS,
+                                                   HB(0, 1, pb), HB(1, 1, pb), HB(0, 1, nb), HB(1, 1, nb), rb,
+                                                   rb + M * HS, hs1, lane, wave, live);
     }
     if (stager && t + 1 < a.T) {
       *reinterpret_cast<uint4*>(XB(0, nb) + my_rr * XS + my_c * 8) = xh;
@@ -600,17 +627,18 @@ __global__ void __launch_bounds__(NW * 64) gru_x3_kernel(GruArgs a) {
 #undef XB
 }
 
-static size_t gru_x3_lds_bytes(int RT, int KSX, int KSH, int NW, int lbr) {
+// masked: the M window words after red
+static size_t gru_x3_lds_bytes(int RT, int KSX, int KSH, int NW, int lbr, int masked = 0) {
   const int M = RT * 16, H = KSH * 32, HS = H + GRU_PAD, XS = KSX * 32 + GRU_PAD;
   return (size_t)8 * M * HS * 2 + (size_t)4 * M * XS * 2 + (lbr ? 0 : (size_t)2 * M * HS * 2) +
-         (size_t)2 * 6 * H * 4 + (size_t)NW * M * 4;
+         (size_t)2 * 6 * H * 4 + (size_t)NW * M * 4 + (masked ? (size_t)M * 4 : 0);
 }
 
 // rows per workgroup (GruArgs.tile_rows: 0 / 16 -> 16): 32 rows (RT = 2, linear_before_reset, tiles
 // within the LDS: 155 KB at H = 256) feed every streamed hi / lo weight fragment to two row
 // tiles; a 4096-row batch then fills 128 CUs, which pays only when another slot's batch runs
 // beside it (the cfg5 bench's per-slot streams, engine/abuse.py overlap).
-template <int KSX, int KSH>
+template <int KSX, int KSH, int MASKED>
 static void launch_gru_x3(const GruArgs& a, hipStream_t st) {
   constexpr int NW = KSH >= 4 ? 8 : 4;
   const dim3 block(NW * 64);
@@ -622,35 +650,35 @@ static void launch_gru_x3(const GruArgs& a, hipStream_t st) {
     // keeps the 8-wave kernel
     if (a.waves != 8 && lbr) {
       const int rt = a.tile_rows == 32 ? 2 : 1;
-      const size_t lds = gru_x3_lds_bytes(rt, KSX, KSH, 16, 1);
+      const size_t lds = gru_x3_lds_bytes(rt, KSX, KSH, 16, 1, MASKED);
       if (rt == 2 && lds <= 160 * 1024) {
-        IGP_LAUNCH((gru_x3_kernel<2, KSX, KSH, 1, 16>), dim3((a.n_rows + 31) / 32), dim3(1024), lds, st, a);
+        IGP_LAUNCH((gru_x3_kernel<2, KSX, KSH, 1, 16, MASKED>), dim3((a.n_rows + 31) / 32), dim3(1024), lds, st, a);
         return;
       }
       if (rt == 1) {
-        IGP_LAUNCH((gru_x3_kernel<1, KSX, KSH, 1, 16>), dim3((a.n_rows + 15) / 16), dim3(1024), lds, st, a);
+        IGP_LAUNCH((gru_x3_kernel<1, KSX, KSH, 1, 16, MASKED>), dim3((a.n_rows + 15) / 16), dim3(1024), lds, st, a);
         return;
       }
     }
   }
-  if (lbr && a.tile_rows == 32 && gru_x3_lds_bytes(2, KSX, KSH, NW, 1) <= 160 * 1024) {
-    IGP_LAUNCH((gru_x3_kernel<2, KSX, KSH, 1, NW>), dim3((a.n_rows + 31) / 32), block,
-               gru_x3_lds_bytes(2, KSX, KSH, NW, 1), st, a);
+  if (lbr && a.tile_rows == 32 && gru_x3_lds_bytes(2, KSX, KSH, NW, 1, MASKED) <= 160 * 1024) {
+    IGP_LAUNCH((gru_x3_kernel<2, KSX, KSH, 1, NW, MASKED>), dim3((a.n_rows + 31) / 32), block,
+               gru_x3_lds_bytes(2, KSX, KSH, NW, 1, MASKED), st, a);
     return;
   }
   const dim3 grid((a.n_rows + 15) / 16);
-  const size_t lds = gru_x3_lds_bytes(1, KSX, KSH, NW, lbr);
+  const size_t lds = gru_x3_lds_bytes(1, KSX, KSH, NW, lbr, MASKED);
   if (lbr)
-    IGP_LAUNCH((gru_x3_kernel<1, KSX, KSH, 1, NW>), grid, block, lds, st, a);
+    IGP_LAUNCH((gru_x3_kernel<1, KSX, KSH, 1, NW, MASKED>), grid, block, lds, st, a);
   else
-    IGP_LAUNCH((gru_x3_kernel<1, KSX, KSH, 0, NW>), grid, block, lds, st, a);
+    IGP_LAUNCH((gru_x3_kernel<1, KSX, KSH, 0, NW, MASKED>), grid, block, lds, st, a);
 }
 
 // Two stacked layers, layer-pipelined: waves [0, NW/2) run layer 1 at step t while waves
 // [NW/2, NW) run layer 2 at step t-1 (it needs h1_{t-1} and h2_{t-2}, both complete after the
 // previous barrier). The two layers' weight-fragment load chains overlap and each step costs
 // one block barrier. Buffers: H1[s] lives in hb1[(s+1)&1], H2[s] in hb2[(s+1)&1], H[-1] = 0.
-template <int RT, int KSX, int KSH, int LBR, int NW>
+template <int RT, int KSX, int KSH, int LBR, int NW, int MASKED = 0>
 __global__ void __launch_bounds__(NW * 64) gru2_pipe_kernel(GruArgs a) {
   constexpr int M = RT * 16;
   constexpr int H = KSH * 32;
@@ -724,6 +752,9 @@ __global__ void __launch_bounds__(NW * 64) gru2_pipe_kernel(GruArgs a) {
     }
     return v;
   };
+  if constexpr (MASKED != 0) {
+    if (stager && my_c == 0) reinterpret_cast<uint32_t*>(red + NW * M)[my_rr] = seq_window(a, grow, n_live, valid_from);
+  }
   __syncthreads();
   if (stager) *reinterpret_cast<uint4*>(XB(0) + my_rr * XS + my_c * 8) = load_x(0);
   float hs[HTW][RT][4];
@@ -737,16 +768,22 @@ __global__ void __launch_bounds__(NW * 64) gru2_pipe_kernel(GruArgs a) {
 
   for (int t = 0; t <= a.T; ++t) {
     const uint4 xn = load_x(t + 1);
+    // each half tests the window against its own step: layer 1 is at t, layer 2 at t - 1
+    SeqLive<MASKED> live;
+    if constexpr (MASKED != 0) {
+      const int ts = t - layer;
+      live = {reinterpret_cast<const uint32_t*>(red + NW * M), (lane >> 4) * 4, a.reverse ? a.T - 1 - ts : ts};
+    }
     if (layer == 0) {
       if (t < a.T)  // H1[t] from x_t and H1[t-1]
-        layer_step<RT, KSX, KSH, LBR, NWL>(w0, r0, bias, XB(t & 1), XS, HB(0, t & 1), HB(0, (t + 1) & 1),
-                                           rb, hs, lane, lw);
+        layer_step<RT, KSX, KSH, LBR, NWL, MASKED>(w0, r0, bias, XB(t & 1), XS, HB(0, t & 1), HB(0, (t + 1) & 1),
+                                                   rb, hs, lane, lw, live);
       else if (LBR == 0)
         __syncthreads();  // match the other half's internal barrier
     } else {
       if (t >= 1)   // H2[t-1] from H1[t-1] and H2[t-2]
-        layer_step<RT, KSH, KSH, LBR, NWL>(w1, r1, bias + 6 * H, HB(0, t & 1), HS, HB(1, (t - 1) & 1),
-                                           HB(1, t & 1), rb + M * HS, hs, lane, lw);
+        layer_step<RT, KSH, KSH, LBR, NWL, MASKED>(w1, r1, bias + 6 * H, HB(0, t & 1), HS, HB(1, (t - 1) & 1),
+                                                   HB(1, t & 1), rb + M * HS, hs, lane, lw, live);
       else if (LBR == 0)
         __syncthreads();
     }
@@ -805,70 +842,100 @@ __global__ void __launch_bounds__(NW * 64) gru2_pipe_kernel(GruArgs a) {
 #undef XB
 }
 
-static size_t gru_pipe_lds_bytes(int RT, int KSX, int KSH, int NW) {
+
+static size_t gru_pipe_lds_bytes(int RT, int KSX, int KSH, int NW, int masked) {
   const int M = RT * 16, H = KSH * 32, HS = H + GRU_PAD, XS = KSX * 32 + GRU_PAD;
   return (size_t)4 * M * HS * 2 + (size_t)2 * M * XS * 2 + (size_t)2 * M * HS * 2 + (size_t)2 * 6 * H * 4 +
-         (size_t)NW * M * 4;
+         (size_t)NW * M * 4 + (masked ? (size_t)M * 4 : 0);
 }
 
-static size_t gru_lds_bytes(int RT, int KSX, int KSH, int NW) {
+static size_t gru_lds_bytes(int RT, int KSX, int KSH, int NW, int masked) {
   const int M = RT * 16, H = KSH * 32, HS = H + GRU_PAD, XS = KSX * 32 + GRU_PAD;
   return (size_t)4 * M * HS * 2 + (size_t)2 * M * XS * 2 + (size_t)M * HS * 2 + (size_t)2 * 6 * H * 4 +
-         (size_t)NW * M * 4;
+         (size_t)NW * M * 4 + (masked ? (size_t)M * 4 : 0);
 }
 
-template <int RT, int KSX, int KSH, int NW>
+template <int RT, int KSX, int KSH, int NW, int MASKED>
 static void launch_gru_w(const GruArgs& a, hipStream_t st) {
   const int M = RT * 16;
   const dim3 grid((a.n_rows + M - 1) / M), block(NW * 64);
-  const size_t lds = gru_lds_bytes(RT, KSX, KSH, NW);
+  const size_t lds = gru_lds_bytes(RT, KSX, KSH, NW, MASKED);
   if (a.layer[0].lbr)
-    IGP_LAUNCH((gru_kernel<RT, KSX, KSH, 1, NW>), grid, block, lds, st, a);
+    IGP_LAUNCH((gru_kernel<RT, KSX, KSH, 1, NW, MASKED>), grid, block, lds, st, a);
   else
-    IGP_LAUNCH((gru_kernel<RT, KSX, KSH, 0, NW>), grid, block, lds, st, a);
+    IGP_LAUNCH((gru_kernel<RT, KSX, KSH, 0, NW, MASKED>), grid, block, lds, st, a);
 }
 
-template <int RT, int KSX, int KSH, int NW>
+template <int RT, int KSX, int KSH, int NW, int MASKED>
 static void launch_gru_pipe(const GruArgs& a, hipStream_t st) {
   const int M = RT * 16;
   const dim3 grid((a.n_rows + M - 1) / M), block(NW * 64);
-  const size_t lds = gru_pipe_lds_bytes(RT, KSX, KSH, NW);
+  const size_t lds = gru_pipe_lds_bytes(RT, KSX, KSH, NW, MASKED);
   if (a.layer[0].lbr)
-    IGP_LAUNCH((gru2_pipe_kernel<RT, KSX, KSH, 1, NW>), grid, block, lds, st, a);
+    IGP_LAUNCH((gru2_pipe_kernel<RT, KSX, KSH, 1, NW, MASKED>), grid, block, lds, st, a);
   else
-    IGP_LAUNCH((gru2_pipe_kernel<RT, KSX, KSH, 0, NW>), grid, block, lds, st, a);
+    IGP_LAUNCH((gru2_pipe_kernel<RT, KSX, KSH, 0, NW, MASKED>), grid, block, lds, st, a);
 }
 
-template <int RT, int KSX, int KSH>
+template <int RT, int KSX, int KSH, int MASKED>
 static void launch_gru_t(const GruArgs& a, hipStream_t st) {
   if (a.n_layers == 2 && a.pipeline) {
     // 2 hidden tiles per wave: H/32 waves per layer (H=256: 16 waves = 1024 threads)
     if constexpr (KSH == 8) {
-      return launch_gru_pipe<RT, KSX, KSH, 16>(a, st);
+      return launch_gru_pipe<RT, KSX, KSH, 16, MASKED>(a, st);
     } else if constexpr (KSH == 4) {
-      return launch_gru_pipe<RT, KSX, KSH, 8>(a, st);
+      return launch_gru_pipe<RT, KSX, KSH, 8, MASKED>(a, st);
     } else {
-      return launch_gru_pipe<RT, KSX, KSH, 4>(a, st);
+      return launch_gru_pipe<RT, KSX, KSH, 4, MASKED>(a, st);
     }
   }
   if constexpr (KSH >= 4) {  // 8 waves: 2 hidden tiles per wave (measured faster than 4 for H >= 128)
-    if (a.waves != 4) return launch_gru_w<RT, KSX, KSH, 8>(a, st);
+    if (a.waves != 4) return launch_gru_w<RT, KSX, KSH, 8, MASKED>(a, st);
   }
-  launch_gru_w<RT, KSX, KSH, 4>(a, st);
+  launch_gru_w<RT, KSX, KSH, 4, MASKED>(a, st);
 }
 
-template <int RT, int KSX>
+template <int RT, int KSX, int MASKED>
 static void launch_gru_h(const GruArgs& a, hipStream_t st) {
   switch (a.H) {
-    case 64: launch_gru_t<RT, KSX, 2>(a, st); break;
-    case 128: launch_gru_t<RT, KSX, 4>(a, st); break;
-    case 256: launch_gru_t<RT, KSX, 8>(a, st); break;
+    case 64: launch_gru_t<RT, KSX, 2, MASKED>(a, st); break;
+    case 128: launch_gru_t<RT, KSX, 4, MASKED>(a, st); break;
+    case 256: launch_gru_t<RT, KSX, 8, MASKED>(a, st); break;
     default: break;
   }
 }
 
+// The batch-parallel kernels: split (gru_x3_kernel) or bf16 (gru_kernel / gru2_pipe_kernel).
+template <int MASKED>
+static void launch_gru_bp(const GruArgs& a, hipStream_t st) {
+  const int ksx = a.layer[0].kx_pad / 32;
+  if (a.split) {
+    switch (a.H) {
+      case 64: if (ksx == 1) launch_gru_x3<1, 2, MASKED>(a, st); else launch_gru_x3<2, 2, MASKED>(a, st); break;
+      case 128: if (ksx == 1) launch_gru_x3<1, 4, MASKED>(a, st); else launch_gru_x3<2, 4, MASKED>(a, st); break;
+      default: if (ksx == 1) launch_gru_x3<1, 8, MASKED>(a, st); else launch_gru_x3<2, 8, MASKED>(a, st); break;
+    }
+    return;
+  }
+  // rows per workgroup: every CU streams the full weight set each step (a per-CU L2 bandwidth
+  // bound, tools/gru_bench.py), so 32 rows amortise each fragment over two MFMA row tiles once
+  // the batch fills the 256 CUs at 32 rows; below that 16 keeps more CUs streaming.
+  const int tr = a.tile_rows ? a.tile_rows : (a.n_rows >= 32 * 256 ? 32 : 16);
+  if (tr == 32) {
+    if (ksx == 1) launch_gru_h<2, 1, MASKED>(a, st); else launch_gru_h<2, 2, MASKED>(a, st);
+  } else {
+    if (ksx == 1) launch_gru_h<1, 1, MASKED>(a, st); else launch_gru_h<1, 2, MASKED>(a, st);
+  }
+}
+
+#ifdef IGP_GRU_MASKED_TU
+// gru_masked.hip: this file again, for the MASKED = 1 instances alone
+void launch_gru_masked(const GruArgs& a, hipStream_t st) { launch_gru_bp<1>(a, st); }
+#else
 void launch_gru(const GruArgs& a, hipStream_t st) {
   if (a.n_rows <= 0) return;
+  // per-row lengths: the batch-parallel kernels only (the cluster kernels have no masked variant)
+  if (a.masked) return launch_gru_masked(a, st);
   static int n_cu = [] {
     int dev = 0, v = 0;
     hipGetDevice(&dev);
@@ -884,13 +951,7 @@ void launch_gru(const GruArgs& a, hipStream_t st) {
     if (a.ws && gru_wsx_eligible(a) && gru_wsx_clusters(a.n_rows) * 16 <= n_cu / 2) {
       return launch_gru_wsx(a, st);
     }
-    const int ksx = a.layer[0].kx_pad / 32;
-    switch (a.H) {
-      case 64: if (ksx == 1) launch_gru_x3<1, 2>(a, st); else launch_gru_x3<2, 2>(a, st); break;
-      case 128: if (ksx == 1) launch_gru_x3<1, 4>(a, st); else launch_gru_x3<2, 4>(a, st); break;
-      default: if (ksx == 1) launch_gru_x3<1, 8>(a, st); else launch_gru_x3<2, 8>(a, st); break;
-    }
-    return;
+    return launch_gru_bp<0>(a, st);
   }
   // weight-stationary clusters while all of them fit one wave of the chip (1 workgroup per CU);
   // beyond that the batch-parallel kernel at 32 rows per workgroup streams weights at a better
@@ -901,16 +962,8 @@ void launch_gru(const GruArgs& a, hipStream_t st) {
       return launch_gru_ws(a, st);
     }
   }
-  // rows per workgroup: every CU streams the full weight set each step (a per-CU L2 bandwidth
-  // bound, tools/gru_bench.py), so 32 rows amortise each fragment over two MFMA row tiles once
-  // the batch fills the 256 CUs at 32 rows; below that 16 keeps more CUs streaming.
-  const int tr = a.tile_rows ? a.tile_rows : (a.n_rows >= 32 * 256 ? 32 : 16);
-  const int ksx = a.layer[0].kx_pad / 32;
-  if (tr == 32) {
-    if (ksx == 1) launch_gru_h<2, 1>(a, st); else launch_gru_h<2, 2>(a, st);
-  } else {
-    if (ksx == 1) launch_gru_h<1, 1>(a, st); else launch_gru_h<1, 2>(a, st);
-  }
+  launch_gru_bp<0>(a, st);
 }
+#endif
 
 }  // namespace igp

@@ -962,7 +962,7 @@ int gru_ws_clusters(int n_rows) { return (n_rows + WS_M - 1) / WS_M; }
 int gru_ws2_clusters(int n_rows) { return (n_rows + W2_M - 1) / W2_M; }
 
 bool gru_ws_eligible(const GruArgs& a) {
-  return a.ws_x && a.ws_sync && a.ws_err && a.n_layers == 2 && a.H == WS_H && a.layer[0].lbr == 1 &&
+  return !a.masked && a.ws_x && a.ws_sync && a.ws_err && a.n_layers == 2 && a.H == WS_H && a.layer[0].lbr == 1 &&
          a.layer[1].lbr == 1 && a.layer[0].kx_pad == 32 && a.I <= 32 && a.T >= 1 && a.T < 32768 &&
          (a.mode != 1 || a.ev_ring <= 65535) &&
          (a.head_w == nullptr || a.ws_part != nullptr) && gru_ws_clusters(a.n_rows) <= a.ws_clusters;

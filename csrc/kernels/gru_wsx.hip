@@ -459,8 +459,8 @@ size_t gru_wsx_lds_bytes() {
 int gru_wsx_clusters(int n_rows) { return (n_rows + X_M - 1) / X_M; }
 
 bool gru_wsx_eligible(const GruArgs& a) {
-  return a.split && a.ws_x && a.ws_sync && a.ws_err && a.n_layers == 2 && a.H == X_H && a.layer[0].lbr == 1 &&
-         a.layer[1].lbr == 1 && a.layer[0].kx_pad == 32 && a.layer[0].W_lo && a.layer[0].R_lo && a.layer[1].W_lo &&
+  return !a.masked && a.split && a.ws_x && a.ws_sync && a.ws_err && a.n_layers == 2 && a.H == X_H &&
+         a.layer[0].lbr == 1 && a.layer[1].lbr == 1 && a.layer[0].kx_pad == 32 && a.layer[0].W_lo && a.layer[0].R_lo && a.layer[1].W_lo &&
          a.layer[1].R_lo && a.I <= 32 && (a.I & 7) == 0 && a.T >= 1 && a.T < 32768 &&
          (a.mode != 1 || a.ev_ring <= 65535) && (a.head_w == nullptr || a.ws_part != nullptr) &&
          gru_wsx_clusters(a.n_rows) <= a.ws_clusters;

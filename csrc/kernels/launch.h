@@ -330,8 +330,14 @@ struct GruArgs {
   int64_t* ws_trace;        // [64][6] phase timestamps of workgroup 0 (nullable; tools/gru_bench.py)
   int32_t split;            // 1: f32-faithful bf16 hi/lo pairs, three MFMAs per product (gru.hip x3)
   int32_t reverse;          // 1: ONNX direction=reverse (every layer): time steps read last to first
+  // ONNX sequence_lens: a row is updated on its live steps only and holds h on every other one.
+  // Live window of actual time indices: mode 0 [0, lens[row]), mode 1 [T - min(ev_count, T), T).
+  // Batch-parallel kernels only (never the weight-stationary clusters); T <= 65535.
+  int32_t masked;
+  const int32_t* lens;      // [rows], mode 0 only (nullable -> every row full length)
 };
 void launch_gru(const GruArgs& a, hipStream_t st);
+void launch_gru_masked(const GruArgs& a, hipStream_t st);  // gru_masked.hip; launch_gru routes a.masked here
 bool gru_ws_eligible(const GruArgs& a);
 void launch_gru_ws(const GruArgs& a, hipStream_t st);
 int gru_ws_clusters(int n_rows);
@@ -374,8 +380,11 @@ struct LstmArgs {
   int32_t tile_rows;        // 0 / 16 | 32 rows per workgroup (32 only where the LDS allows)
   int32_t split;            // 1: f32-faithful bf16 hi/lo pairs, three MFMAs per product
   int32_t reverse;          // 1: ONNX direction=reverse: time steps read last to first
+  int32_t masked;           // ONNX sequence_lens, as GruArgs.masked (h and c are held)
+  const int32_t* lens;      // [rows], mode 0 only (nullable -> every row full length)
 };
 void launch_lstm(const LstmArgs& a, hipStream_t st);
+void launch_lstm_masked(const LstmArgs& a, hipStream_t st);  // lstm_masked.hip; launch_lstm routes a.masked here
 // rows per workgroup launch_lstm uses (16, or 32 when requested and the activation tiles fit the LDS)
 int lstm_tile_rows(int H, int kx_pad, int split, int requested);
 

@@ -17,6 +17,7 @@
 // SPLIT = 0 (bf16 plans): one MFMA per product.
 #include "common.h"
 #include "launch.h"
+#include "seq_window.h"
 
 namespace igp {
 
@@ -107,12 +108,14 @@ __device__ __forceinline__ void gate_products(f32x4 (&acc)[4][RT], const WPair& 
 
 // One LSTM layer step for this wave's hidden tiles. KSI / KSH: K/32 of the input / hidden parts;
 // bias: [4H] with Wb + Rb already summed per gate.
-template <int RT, int KSI, int KSH, int NW, int SPLIT>
+// MASKED: live(rt, r) says whether accumulator row rt*16 + crow + r is inside its window at this
+// step; a dead row keeps h and c and carries h's bf16 (hi / lo) value into hnext.
+template <int RT, int KSI, int KSH, int NW, int SPLIT, int MASKED = 0>
 __device__ __forceinline__ void lstm_step(const WPair& gW, const WPair& gR, const float* bias, const uint16_t* in,
                                           const uint16_t* inl, int in_stride, const uint16_t* hprev,
                                           const uint16_t* hprevl, uint16_t* hnext, uint16_t* hnextl,
                                           float (&hs)[KSH * 2 / NW][RT][4], float (&cs)[KSH * 2 / NW][RT][4],
-                                          int lane, int wave) {
+                                          int lane, int wave, const SeqLive<MASKED>& live) {
   constexpr int HT = KSH * 2;      // hidden tiles of 16 units
   constexpr int HTW = HT / NW;     // per wave
   constexpr int H = KSH * 32;
@@ -139,8 +142,13 @@ __device__ __forceinline__ void lstm_step(const WPair& gW, const WPair& gR, cons
         const float og = sig_(acc[1][rt][r] + bo);
         const float fg = sig_(acc[2][rt][r] + bf);
         const float ct = tanh_(acc[3][rt][r] + bc);
-        const float c = fg * cs[i][rt][r] + ig * ct;
-        const float h = og * tanh_(c);
+        float c = fg * cs[i][rt][r] + ig * ct;
+        float h = og * tanh_(c);
+        if constexpr (MASKED != 0) {
+          const bool on = live(rt, r);
+          c = on ? c : cs[i][rt][r];
+          h = on ? h : hs[i][rt][r];
+        }
         cs[i][rt][r] = c;
         hs[i][rt][r] = h;
         const int o = (rt * 16 + crow + r) * HS + j;
@@ -200,7 +208,10 @@ __device__ __forceinline__ void emit_outputs(const LstmArgs& a, float (&hs)[KSH 
   }
 }
 
-template <int RT, int KSX, int KSH, int NW, int SPLIT>
+// MASKED: per-row sequence lengths. The my_c == 0 stager of each row publishes the row's live
+// window in LDS (wl[M], after red); every step each lane tests the windows of its accumulator
+// rows (SeqLive). Dead steps skip nothing: the barriers stay block-uniform.
+template <int RT, int KSX, int KSH, int NW, int SPLIT, int MASKED = 0>
 __global__ void __launch_bounds__(NW * 64) lstm_kernel(LstmArgs a) {
   constexpr int M = RT * 16;
   constexpr int H = KSH * 32;
@@ -297,6 +308,9 @@ __global__ void __launch_bounds__(NW * 64) lstm_kernel(LstmArgs a) {
     *reinterpret_cast<uint4*>(XB(0, b) + my_rr * XS + my_c * 8) = hi;
     if constexpr (SPLIT != 0) *reinterpret_cast<uint4*>(XB(1, b) + my_rr * XS + my_c * 8) = lo;
   };
+  if constexpr (MASKED != 0) {
+    if (stager && my_c == 0) reinterpret_cast<uint32_t*>(red + NW * M)[my_rr] = seq_window(a, grow, n_live, valid_from);
+  }
   __syncthreads();  // zeroing done before the first staged row lands
   if (stager) {
     uint4 h, l;
@@ -316,14 +330,18 @@ __global__ void __launch_bounds__(NW * 64) lstm_kernel(LstmArgs a) {
   constexpr int LO = SPLIT ? 1 : 0;
   for (int t = 0; t < a.T; ++t) {
     const int pb = t & 1, nb = pb ^ 1;
+    SeqLive<MASKED> live;
+    if constexpr (MASKED != 0)
+      live = {reinterpret_cast<const uint32_t*>(red + NW * M), (lane >> 4) * 4, a.reverse ? a.T - 1 - t : t};
     uint4 xh, xl;
     load_x(t + 1, xh, xl);
-    lstm_step<RT, KSX, KSH, NW, SPLIT>(w0, r0, bias, XB(0, pb), XB(LO, pb), XS, HB(0, 0, pb), HB(LO, 0, pb),
-                                       HB(0, 0, nb), HB(LO, 0, nb), hs0, cs0, lane, wave);
+    lstm_step<RT, KSX, KSH, NW, SPLIT, MASKED>(w0, r0, bias, XB(0, pb), XB(LO, pb), XS, HB(0, 0, pb), HB(LO, 0, pb),
+                                               HB(0, 0, nb), HB(LO, 0, nb), hs0, cs0, lane, wave, live);
     __syncthreads();
     if (two) {
-      lstm_step<RT, KSH, KSH, NW, SPLIT>(w1, r1, bias + 4 * H, HB(0, 0, nb), HB(LO, 0, nb), HS, HB(0, 1, pb),
-                                         HB(LO, 1, pb), HB(0, 1, nb), HB(LO, 1, nb), hs1, cs1, lane, wave);
+      lstm_step<RT, KSH, KSH, NW, SPLIT, MASKED>(w1, r1, bias + 4 * H, HB(0, 0, nb), HB(LO, 0, nb), HS, HB(0, 1, pb),
+                                                 HB(LO, 1, pb), HB(0, 1, nb), HB(LO, 1, nb), hs1, cs1, lane, wave,
+                                                 live);
     }
     if (stager && t + 1 < a.T) store_x(nb, xh, xl);
     __syncthreads();
@@ -338,9 +356,11 @@ __global__ void __launch_bounds__(NW * 64) lstm_kernel(LstmArgs a) {
 #undef XB
 }
 
-size_t lstm_lds_bytes(int RT, int KSX, int KSH, int NW, int split) {
+// masked: the M window words after red
+size_t lstm_lds_bytes(int RT, int KSX, int KSH, int NW, int split, int masked = 0) {
   const int M = RT * 16, H = KSH * 32, HS = H + LSTM_PAD, XS = KSX * 32 + LSTM_PAD, NH = split ? 2 : 1;
-  return (size_t)NH * (4 * M * HS + 2 * M * XS) * 2 + (size_t)2 * 4 * H * 4 + (size_t)NW * M * 4;
+  return (size_t)NH * (4 * M * HS + 2 * M * XS) * 2 + (size_t)2 * 4 * H * 4 + (size_t)NW * M * 4 +
+         (masked ? (size_t)M * 4 : 0);
 }
 
 constexpr size_t kLdsLimit = 160 * 1024;
@@ -348,35 +368,52 @@ constexpr size_t kLdsLimit = 160 * 1024;
 // waves per workgroup: two hidden tiles per wave from H = 128 up (as the GRU kernels), one at H = 64
 constexpr int lstm_waves(int KSH) { return KSH >= 4 ? 8 : 4; }
 
-template <int KSX, int KSH, int SPLIT>
+// The 32-row choice is made on the unmasked footprint (lstm_tile_rows), so a masked launch takes
+// the same tile as its unmasked twin; the window words must then fit too.
+template <int KSX, int KSH, int SPLIT, int MASKED>
 void launch_lstm_t(const LstmArgs& a, hipStream_t st) {
   constexpr int NW = lstm_waves(KSH);
   const dim3 block(NW * 64);
   // 32 rows per workgroup feed every streamed weight fragment to two row tiles; only on request
   // (tile_rows = 32) and only where the doubled activation tiles stay within the LDS
-  if (a.tile_rows == 32 && lstm_lds_bytes(2, KSX, KSH, NW, SPLIT) <= kLdsLimit) {
-    IGP_LAUNCH((lstm_kernel<2, KSX, KSH, NW, SPLIT>), dim3((a.n_rows + 31) / 32), block,
-               lstm_lds_bytes(2, KSX, KSH, NW, SPLIT), st, a);
+  if (a.tile_rows == 32 && lstm_lds_bytes(2, KSX, KSH, NW, SPLIT) <= kLdsLimit &&
+      lstm_lds_bytes(2, KSX, KSH, NW, SPLIT, MASKED) <= kLdsLimit) {
+    IGP_LAUNCH((lstm_kernel<2, KSX, KSH, NW, SPLIT, MASKED>), dim3((a.n_rows + 31) / 32), block,
+               lstm_lds_bytes(2, KSX, KSH, NW, SPLIT, MASKED), st, a);
     return;
   }
-  IGP_LAUNCH((lstm_kernel<1, KSX, KSH, NW, SPLIT>), dim3((a.n_rows + 15) / 16), block,
-             lstm_lds_bytes(1, KSX, KSH, NW, SPLIT), st, a);
+  IGP_LAUNCH((lstm_kernel<1, KSX, KSH, NW, SPLIT, MASKED>), dim3((a.n_rows + 15) / 16), block,
+             lstm_lds_bytes(1, KSX, KSH, NW, SPLIT, MASKED), st, a);
 }
 
-template <int KSX, int KSH>
+template <int KSX, int KSH, int MASKED>
 void launch_lstm_s(const LstmArgs& a, hipStream_t st) {
-  if (a.split) launch_lstm_t<KSX, KSH, 1>(a, st);
-  else launch_lstm_t<KSX, KSH, 0>(a, st);
+  if (a.split) launch_lstm_t<KSX, KSH, 1, MASKED>(a, st);
+  else launch_lstm_t<KSX, KSH, 0, MASKED>(a, st);
 }
 
-template <int KSH>
+template <int KSH, int MASKED>
 void launch_lstm_h(const LstmArgs& a, hipStream_t st) {
-  if (a.layer[0].kx_pad == 32) launch_lstm_s<1, KSH>(a, st);
-  else launch_lstm_s<2, KSH>(a, st);
+  if (a.layer[0].kx_pad == 32) launch_lstm_s<1, KSH, MASKED>(a, st);
+  else launch_lstm_s<2, KSH, MASKED>(a, st);
+}
+
+template <int MASKED>
+void launch_lstm_m(const LstmArgs& a, hipStream_t st) {
+  switch (a.H) {
+    case 64: launch_lstm_h<2, MASKED>(a, st); break;
+    case 128: launch_lstm_h<4, MASKED>(a, st); break;
+    case 256: launch_lstm_h<8, MASKED>(a, st); break;
+    default: break;
+  }
 }
 
 }  // namespace
 
+#ifdef IGP_LSTM_MASKED_TU
+// lstm_masked.hip: this file again, for the MASKED = 1 instances alone
+void launch_lstm_masked(const LstmArgs& a, hipStream_t st) { launch_lstm_m<1>(a, st); }
+#else
 int lstm_tile_rows(int H, int kx_pad, int split, int requested) {
   const int KSH = H / 32;
   return requested == 32 && lstm_lds_bytes(2, kx_pad / 32, KSH, lstm_waves(KSH), split) <= kLdsLimit ? 32 : 16;
@@ -384,12 +421,9 @@ int lstm_tile_rows(int H, int kx_pad, int split, int requested) {
 
 void launch_lstm(const LstmArgs& a, hipStream_t st) {
   if (a.n_rows <= 0) return;
-  switch (a.H) {
-    case 64: launch_lstm_h<2>(a, st); break;
-    case 128: launch_lstm_h<4>(a, st); break;
-    case 256: launch_lstm_h<8>(a, st); break;
-    default: break;
-  }
+  if (a.masked) return launch_lstm_masked(a, st);
+  launch_lstm_m<0>(a, st);
 }
+#endif
 
 }  // namespace igp

@@ -115,8 +115,10 @@ void CpuLtvDevice::run(Slot& s, int n) {
 
 // ============================================================================ abuse
 CpuAbuseDevice::CpuAbuseDevice(std::shared_ptr<CpuScorer> sc, std::shared_ptr<exec::Executor> model,
-                               std::string in_name, std::string out_name, int depth, int cap)
-    : sc_(std::move(sc)), model_(std::move(model)), in_(std::move(in_name)), out_(std::move(out_name)) {
+                               std::string in_name, std::string out_name, int depth, int cap,
+                               std::string lens_name)
+    : sc_(std::move(sc)), model_(std::move(model)), in_(std::move(in_name)), out_(std::move(out_name)),
+      lens_(std::move(lens_name)) {
   if (!sc_ || depth < 1 || cap < 1) throw std::runtime_error("CpuAbuseDevice: arguments");
   slots_.resize(size_t(depth));
   for (auto& s : slots_) {
@@ -160,23 +162,43 @@ void CpuAbuseDevice::run(Slot& s, int n, int64_t now) {
   if (!model_ || n == 0) return;
   // engine/abuse.py model_scores (executor path): X [event_ring][n][event_dim], each account's
   // history oldest first, right-aligned (zeros for an unknown account)
-  const int T = sc_->event_ring(), D = sc_->event_dim();
+  // A model with a sequence_lens input (lens_): each history left-aligned in the model's own
+  // window (its last min(count, T) events, T the model's sequence length when it is fixed and
+  // shorter than the ring) with its length, so a short history is scored on its events alone.
+  const int ring = sc_->event_ring(), D = sc_->event_dim();
+  int T = ring;
+  if (!lens_.empty())
+    for (const auto& vi : model_->model().graph.inputs)
+      if (vi.name == in_ && vi.dims.size() == 3 && vi.dims[0] > 0 && vi.dims[0] < ring) T = int(vi.dims[0]);
   onnx::Tensor x;
   x.name = in_;
   x.dtype = onnx::FLOAT;
   x.dims = {T, n, D};
   x.f.assign(size_t(T) * size_t(n) * size_t(D), 0.f);
-  std::vector<float> h(size_t(T) * size_t(D));
+  std::vector<float> h(size_t(ring) * size_t(D));
+  onnx::Tensor lens;
+  if (!lens_.empty()) {
+    lens.name = lens_;
+    lens.dtype = onnx::INT32;
+    lens.dims = {n};
+    lens.i.assign(size_t(n), 0);
+  }
   for (int i = 0; i < n; ++i) {
     const int32_t sl = s.slots[size_t(i)];
     if (sl < 0) continue;
     sc_->event_history(sl, h.data());
+    if (!lens_.empty()) {
+      lens.i[size_t(i)] = left_align_history(h.data(), ring, D, sc_->event_count(sl), T, &x.f[size_t(i) * size_t(D)],
+                                             size_t(n) * size_t(D));
+      continue;
+    }
     for (int t = 0; t < T; ++t)
       std::memcpy(&x.f[(size_t(t) * size_t(n) + size_t(i)) * size_t(D)], &h[size_t(t) * size_t(D)],
                   sizeof(float) * size_t(D));
   }
   std::map<std::string, onnx::Tensor> in;
   in.emplace(in_, std::move(x));
+  if (!lens_.empty()) in.emplace(lens_, std::move(lens));
   const auto y = model_->run(in);
   const onnx::Tensor& t = pick_output(*model_, y, out_);
   if (int64_t(t.f.size()) < n) throw std::runtime_error("CpuAbuseDevice: model output too short");

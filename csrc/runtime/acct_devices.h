@@ -50,8 +50,9 @@ class CpuLtvDevice {
 
 class CpuAbuseDevice {
  public:
+  // lens_name: the model's sequence_lens graph input; empty: an unmasked model (zero-padded histories)
   CpuAbuseDevice(std::shared_ptr<CpuScorer> sc, std::shared_ptr<exec::Executor> model, std::string in_name,
-                 std::string out_name, int depth, int cap);
+                 std::string out_name, int depth, int cap, std::string lens_name = "");
   const IgpModelOps* ops() const { return &ops_; }
 
  private:
@@ -63,7 +64,7 @@ class CpuAbuseDevice {
   void run(Slot& s, int n, int64_t now);
   std::shared_ptr<CpuScorer> sc_;
   std::shared_ptr<exec::Executor> model_;
-  std::string in_, out_;
+  std::string in_, out_, lens_;
   std::vector<Slot> slots_;
   IgpModelOps ops_{};
 };

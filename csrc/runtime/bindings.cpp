@@ -65,7 +65,8 @@ onnx::Tensor np_to_tensor(const std::string& name, py::array arr) {
   for (py::ssize_t d = 0; d < arr.ndim(); ++d) t.dims.push_back(arr.shape(d));
   if (py::isinstance<py::array_t<int64_t>>(arr) || arr.dtype().kind() == 'i') {
     auto a = py::array_t<int64_t, py::array::c_style | py::array::forcecast>(arr);
-    t.dtype = onnx::INT64;
+    // an int32 array keeps its element type (ONNX types GRU / LSTM sequence_lens tensor(int32))
+    t.dtype = arr.dtype().kind() == 'i' && arr.itemsize() == 4 ? onnx::INT32 : onnx::INT64;
     t.i.assign(a.data(), a.data() + a.size());
   } else {
     auto a = py::array_t<float, py::array::c_style | py::array::forcecast>(arr);
@@ -542,6 +543,7 @@ PYBIND11_MODULE(_native, m) {
         std::memcpy(out.mutable_data(), &f, sizeof f);
         return out;
       })
+      .def("event_count", [](CpuScorer& c, int32_t slot) { return c.event_count(slot); })
       .def("event_history", [](CpuScorer& c, int32_t slot) {
         py::array_t<float> out({(py::ssize_t)c.event_ring(), (py::ssize_t)c.event_dim()});
         c.event_history(slot, out.mutable_data());
@@ -988,9 +990,10 @@ PYBIND11_MODULE(_native, m) {
            py::arg("out_name") = "output", py::arg("width") = 0, py::arg("depth") = 2, py::arg("cap") = 4096)
       .def("model_ops", [](const CpuLtvDevice& d) { return reinterpret_cast<uintptr_t>(d.ops()); });
   py::class_<CpuAbuseDevice, std::shared_ptr<CpuAbuseDevice>>(m, "CpuAbuseDevice")
-      .def(py::init<std::shared_ptr<CpuScorer>, std::shared_ptr<exec::Executor>, std::string, std::string, int, int>(),
+      .def(py::init<std::shared_ptr<CpuScorer>, std::shared_ptr<exec::Executor>, std::string, std::string, int, int,
+                    std::string>(),
            py::arg("scorer"), py::arg("model"), py::arg("in_name") = "input", py::arg("out_name") = "output",
-           py::arg("depth") = 2, py::arg("cap") = 4096)
+           py::arg("depth") = 2, py::arg("cap") = 4096, py::arg("lens_name") = "")
       .def("model_ops", [](const CpuAbuseDevice& d) { return reinterpret_cast<uintptr_t>(d.ops()); });
 
   py::class_<PyAcct, std::shared_ptr<PyAcct>>(m, "AcctRouter")

@@ -428,4 +428,10 @@ void CpuScorer::event_history(int32_t slot, float* out) const {
   }
 }
 
+int CpuScorer::event_count(int32_t slot) const {
+  std::lock_guard<std::mutex> g(mu_);
+  if (slot < 0 || slot >= cap_) return 0;
+  return rt[slot].ev_count < ER_ ? rt[slot].ev_count : ER_;
+}
+
 }  // namespace igp

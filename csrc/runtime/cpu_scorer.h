@@ -9,6 +9,7 @@
 // first and applies the batch's events afterwards in request order (the device semantics).
 #pragma once
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -42,6 +43,8 @@ class CpuScorer {
   FeatRec features(int32_t slot, int64_t now);
   // event history, oldest first, right-aligned: out[event_ring * event_dim]
   void event_history(int32_t slot, float* out) const;
+  // events held for the account: min(ev_count, event_ring); 0 for an unknown slot
+  int event_count(int32_t slot) const;
 
   int64_t capacity() const { return cap_; }
   int ring_size() const { return R_; }
@@ -73,5 +76,18 @@ class CpuScorer {
   int ml_col_ = 0;
   mutable std::mutex mu_;
 };
+
+// Input of a sequence model that reads ONNX sequence_lens: the right-aligned zero-padded history
+// hist [ring][dim] (event_history) with ``count`` events becomes the left-aligned window
+// out[t * stride .. + dim], t < T - its last min(count, T) events from step 0 on, the rest left as
+// it is (zero) - and the returned length (engine/abuse.py left_align_history is the Python twin).
+inline int32_t left_align_history(const float* hist, int ring, int dim, int count, int T, float* out, size_t stride) {
+  int n = count < ring ? count : ring;
+  if (n > T) n = T;
+  if (n < 0) n = 0;
+  for (int t = 0; t < n; ++t)
+    std::memcpy(out + size_t(t) * stride, hist + size_t(ring - n + t) * size_t(dim), sizeof(float) * size_t(dim));
+  return n;
+}
 
 }  // namespace igp

@@ -29,7 +29,7 @@ std::vector<float> as_float(const Tensor& t) {
 }
 
 std::vector<int64_t> as_int(const Tensor& t) {
-  if (t.dtype == INT64) return t.i;
+  if (t.dtype == INT64 || t.dtype == onnx::INT32) return t.i;
   std::vector<int64_t> r;
   for (float v : t.f) r.push_back(int64_t(v));
   return r;
@@ -126,11 +126,31 @@ Tensor matmul(const Tensor& A, const Tensor& B) {
   return Y;
 }
 
+// The lengths of a GRU / LSTM node's optional sequence_lens input [B] (int32, each in [0, S]); S
+// for every row without one.
+std::vector<int64_t> seq_lens(const char* op, const Tensor* lens, int64_t Bn, int64_t S) {
+  std::vector<int64_t> len(Bn, S);
+  if (!lens) return len;
+  const std::string o(op);
+  if (lens->dtype != onnx::INT32) throw std::runtime_error(o + ": sequence_lens must be an int32 tensor");
+  if (lens->dims.size() != 1 || lens->dims[0] != Bn || int64_t(lens->i.size()) != Bn)
+    throw std::runtime_error(o + ": sequence_lens must hold one length per batch row");
+  for (int64_t b = 0; b < Bn; ++b) {
+    if (lens->i[b] < 0 || lens->i[b] > S)
+      throw std::runtime_error(o + ": sequence_lens value " + std::to_string(lens->i[b]) + " is outside [0, " +
+                               std::to_string(S) + "]");
+    len[b] = lens->i[b];
+  }
+  return len;
+}
+
 // ONNX GRU (gates z, r, h), activations sigmoid/tanh, directions forward / reverse /
 // bidirectional. layout 0: X [S][B][I], Y [S][D][B][H], Y_h / initial_h [D][B][H];
 // layout 1 (batch-major): X [B][S][I], Y [B][S][D][H], Y_h / initial_h [B][D][H].
+// sequence_lens: row b is updated on the steps whose time index t < lens[b] and holds its state on
+// the others (reverse starts at t = lens[b] - 1); Y stays zero there, Y_h is the held state.
 void gru(const onnx::Node& n, const Tensor& X, const Tensor& W, const Tensor& R, const Tensor* Bp,
-         const Tensor* h0, Tensor& Y, Tensor& Yh) {
+         const Tensor* lens, const Tensor* h0, Tensor& Y, Tensor& Yh) {
   const int64_t H = n.geti("hidden_size", R.dims.back());
   const bool lbr = n.geti("linear_before_reset", 0);
   const int64_t layout = n.geti("layout", 0);
@@ -149,6 +169,7 @@ void gru(const onnx::Node& n, const Tensor& X, const Tensor& W, const Tensor& R,
   auto yo = [&](int64_t t, int64_t d, int64_t b) { return (layout ? (b * S + t) * D + d : (t * D + d) * Bn + b) * H; };
   auto ho = [&](int64_t d, int64_t b) { return (layout ? b * D + d : d * Bn + b) * H; };
   std::vector<double> hz(H), hr(H), hh(H), xz(H), xr(H), xh(H);
+  const std::vector<int64_t> len = seq_lens("GRU", lens, Bn, S);
   for (int64_t d = 0; d < D; ++d) {
     const bool rev = dir == "reverse" || (D == 2 && d == 1);
     const float* w = &W.f[d * 3 * H * I];
@@ -160,6 +181,7 @@ void gru(const onnx::Node& n, const Tensor& X, const Tensor& W, const Tensor& R,
       if (h0) std::copy(h0->f.begin() + ho(d, b), h0->f.begin() + ho(d, b) + H, h.begin());
       for (int64_t st = 0; st < S; ++st) {
         const int64_t t = rev ? S - 1 - st : st;
+        if (t >= len[b]) continue;
         const float* x = &X.f[xo(t, b)];
         for (int64_t j = 0; j < H; ++j) {
           double az = 0, ar = 0, ah = 0, bz = 0, br = 0, bh = 0;
@@ -205,7 +227,8 @@ void gru(const onnx::Node& n, const Tensor& X, const Tensor& W, const Tensor& R,
 // P [D][3H] (i, o, f), directions and layouts as for the GRU above; Y_c / initial_c are shaped
 // like Y_h / initial_h. Products accumulate in double, the gates are float, as in gru().
 void lstm(const onnx::Node& n, const Tensor& X, const Tensor& W, const Tensor& R, const Tensor* Bp,
-          const Tensor* h0, const Tensor* c0, const Tensor* Pp, Tensor& Y, Tensor& Yh, Tensor& Yc) {
+          const Tensor* lens, const Tensor* h0, const Tensor* c0, const Tensor* Pp, Tensor& Y, Tensor& Yh,
+          Tensor& Yc) {
   const int64_t H = n.geti("hidden_size", R.dims.back());
   const int64_t layout = n.geti("layout", 0);
   if (layout != 0 && layout != 1) throw std::runtime_error("LSTM: layout must be 0 or 1");
@@ -238,6 +261,7 @@ void lstm(const onnx::Node& n, const Tensor& X, const Tensor& W, const Tensor& R
   auto yo = [&](int64_t t, int64_t d, int64_t b) { return (layout ? (b * S + t) * D + d : (t * D + d) * Bn + b) * H; };
   auto ho = [&](int64_t d, int64_t b) { return (layout ? b * D + d : d * Bn + b) * H; };
   std::vector<double> g(4 * H);
+  const std::vector<int64_t> len = seq_lens("LSTM", lens, Bn, S);
   for (int64_t d = 0; d < D; ++d) {
     const bool rev = dir == "reverse" || (D == 2 && d == 1);
     const float* w = &W.f[d * 4 * H * I];
@@ -251,6 +275,7 @@ void lstm(const onnx::Node& n, const Tensor& X, const Tensor& W, const Tensor& R
       if (c0) std::copy(c0->f.begin() + ho(d, b), c0->f.begin() + ho(d, b) + H, c.begin());
       for (int64_t st = 0; st < S; ++st) {
         const int64_t t = rev ? S - 1 - st : st;
+        if (t >= len[b]) continue;
         const float* x = &X.f[xo(t, b)];
         for (int64_t j = 0; j < 4 * H; ++j) {  // rows of W / R: i | o | f | c
           double ax = 0, ah = 0;
@@ -744,19 +769,17 @@ std::map<std::string, Tensor> Executor::run(const std::map<std::string, Tensor>&
       out.f = as_float(x);
     } else if (op == "GRU") {
       Tensor Y, Yh;
-      gru(n, get(n.inputs[0]), get(n.inputs[1]), get(n.inputs[2]), opt(n, 3),
+      gru(n, get(n.inputs[0]), get(n.inputs[1]), get(n.inputs[2]), opt(n, 3), opt(n, 4),
           opt(n, 5), Y, Yh);
-      if (opt(n, 4)) throw std::runtime_error("GRU: sequence_lens is not supported");
       if (!n.outputs.empty() && !n.outputs[0].empty()) vals[n.outputs[0]] = Y;
       if (n.outputs.size() > 1 && !n.outputs[1].empty()) vals[n.outputs[1]] = Yh;
       continue;
     } else if (op == "LSTM") {
       // inputs: X, W, R, B, sequence_lens, initial_h, initial_c, P; outputs: Y, Y_h, Y_c
       if (n.inputs.size() < 3) throw std::runtime_error("LSTM: needs X, W and R");
-      if (opt(n, 4)) throw std::runtime_error("LSTM: sequence_lens is not supported");
       Tensor Y, Yh, Yc;
-      lstm(n, get(n.inputs[0]), get(n.inputs[1]), get(n.inputs[2]), opt(n, 3), opt(n, 5), opt(n, 6), opt(n, 7),
-           Y, Yh, Yc);
+      lstm(n, get(n.inputs[0]), get(n.inputs[1]), get(n.inputs[2]), opt(n, 3), opt(n, 4), opt(n, 5), opt(n, 6),
+           opt(n, 7), Y, Yh, Yc);
       if (!n.outputs.empty() && !n.outputs[0].empty()) vals[n.outputs[0]] = Y;
       if (n.outputs.size() > 1 && !n.outputs[1].empty()) vals[n.outputs[1]] = Yh;
       if (n.outputs.size() > 2 && !n.outputs[2].empty()) vals[n.outputs[2]] = Yc;

@@ -47,9 +47,21 @@ def _headers_mtime():
     return max((os.path.getmtime(h) for h in hs), default=0.0)
 
 
+def _src_mtime(src):
+    """mtime of ``src`` and of the sibling sources it includes (gru_masked.hip includes gru.hip)."""
+    m = os.path.getmtime(src)
+    with open(src, encoding="utf-8", errors="replace") as f:
+        for line in f:
+            if line.startswith('#include "') and line.rstrip().endswith(('.hip"', '.cpp"')):
+                inc = os.path.join(os.path.dirname(src), line.split('"')[1])
+                if os.path.exists(inc):
+                    m = max(m, os.path.getmtime(inc))
+    return m
+
+
 def _compile(cmd, src, obj, force):
     if not force and os.path.exists(obj):
-        if os.path.getmtime(obj) >= max(os.path.getmtime(src), _headers_mtime()):
+        if os.path.getmtime(obj) >= max(_src_mtime(src), _headers_mtime()):
             return obj, 0.0, ""
     os.makedirs(os.path.dirname(obj), exist_ok=True)
     t = time.time()

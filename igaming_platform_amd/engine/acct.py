@@ -258,9 +258,12 @@ def cpu_ltv_device(ltv, owner: int, cap: int, depth: int = 2):
 
 
 def cpu_abuse_device(backend, model, cap: int, in_name: str = "input", out_name: str = "output", depth: int = 2):
-    """CPU abuse device over a CpuBackend's C++ scorer (features + event histories)."""
+    """CPU abuse device over a CpuBackend's C++ scorer (features + event histories). A model that
+    reads ONNX sequence_lens is fed left-aligned histories with their lengths (lens_name)."""
+    from ..models.plan import sequence_lens_input
     ex = native().Executor(model) if model is not None else None
-    return native().CpuAbuseDevice(backend.sc, ex, in_name, out_name, int(depth), int(cap))
+    lens = (sequence_lens_input(model) or "") if model is not None else ""
+    return native().CpuAbuseDevice(backend.sc, ex, in_name, out_name, int(depth), int(cap), lens)
 
 
 class NativeAcct:

@@ -215,6 +215,10 @@ class CpuBackend:
         with self._lock:
             return self.store.event_history(str(slot))
 
+    def event_count(self, slot: int) -> int:
+        with self._lock:
+            return self.store.event_count(str(slot))
+
     def metrics(self) -> Optional[np.ndarray]:
         return None
 
@@ -648,6 +652,15 @@ class GpuBackend:
             out[R - cnt:] = ev[idx]
         return out
 
+    def event_count(self, slot: int) -> int:
+        """Events held for the account (at most the ring)."""
+        torch = self.torch
+        st = self.scorer.stream
+        with self._lock, torch.cuda.stream(st):
+            self.wait_state(st)
+            rt = self.store.read_rt(slot)
+        return min(int(rt["ev_count"]), int(self.store.ev.shape[1]))
+
     def metrics(self) -> np.ndarray:
         return self.scorer.read_metrics()
 
@@ -785,6 +798,9 @@ class NativeCpuBackend:
 
     def event_history(self, slot: int) -> np.ndarray:
         return self.sc.event_history(int(slot))
+
+    def event_count(self, slot: int) -> int:
+        return int(self.sc.event_count(int(slot)))
 
     def metrics(self):
         return None

@@ -52,6 +52,16 @@ def _load_onnx(src):
     return src
 
 
+def _abuse_lens(am, cfg) -> dict:
+    """AbuseService arguments for an executor-run abuse model that reads ONNX sequence_lens."""
+    if am is None:
+        return {}
+    from ..models.plan import sequence_lens_input
+    from .abuse import model_window
+    name = sequence_lens_input(am)
+    return dict(lens_input=name, window=model_window(am, "input", cfg.features.event_ring)) if name else {}
+
+
 class RiskEngine:
     def __init__(self, cfg: Optional[Config] = None, backend: str = "auto", devices: Optional[Sequence[int]] = None,
                  capacity: Optional[int] = None, fraud_model=None, ltv_model=None, abuse_model=None,
@@ -205,7 +215,7 @@ class RiskEngine:
             self.group.runner.ltv = self.ltv
             self.abuse = AbuseService(self, threshold=cfg.abuse.threshold, group=self.group,
                                       executor=N.Executor(am) if (am is not None and backend != "gpu") else None,
-                                      group_model=am is not None and backend == "gpu")
+                                      group_model=am is not None and backend == "gpu", **_abuse_lens(am, cfg))
         elif backend == "gpu":
             from ..models.plan import compile_onnx, to_device
             lg = []
@@ -230,7 +240,7 @@ class RiskEngine:
             self.ltv = LtvService(self.registry, world, executor=N.Executor(lm) if lm is not None else None,
                                   model_width=ltv_width)
             self.abuse = AbuseService(self, threshold=cfg.abuse.threshold,
-                                      executor=N.Executor(am) if am is not None else None)
+                                      executor=N.Executor(am) if am is not None else None, **_abuse_lens(am, cfg))
         # ---- native account RPCs (engine/acct.py, csrc/runtime/acct_core.cpp): PredictLTV,
         # GetPlayerSegment and CheckBonusAbuse bytes -> bytes without Python, micro-batched on this
         # process's model devices (SPMD: the node's router, owner-routed over /dev/shm)

@@ -42,7 +42,11 @@ class GruModel:
       head as a dense launch.
 
     Input: dense X f32 [T, rows, I] (the ONNX layout-0 order; layout-1 plans are fed the same,
-    see :meth:`DeviceModel.run`) or the store's event rings for ``slots``."""
+    see :meth:`DeviceModel.run`) or the store's event rings for ``slots``.
+
+    A plan whose layers read ONNX ``sequence_lens`` gives masked packs (``masked``): short rows hold
+    their state outside their live steps. Dense input takes the lengths as ``lens`` (int32 [rows];
+    None: every row is ``T`` steps long), ring input takes them from the accounts' event counts."""
 
     kind = "gru"     # the plan step kind, weight pack and launch of the cell (LstmModel overrides)
     pack = K.GruPack
@@ -75,22 +79,30 @@ class GruModel:
         return self.head is not None
 
     @property
+    def masked(self) -> bool:
+        return self.packs[0].masked
+
+    @property
     def split(self) -> bool:
         """f32-faithful (bf16 hi/lo, three MFMAs per product) weights."""
         return self.packs[0].split
 
     def run(self, n_rows: int, T: int, out: torch.Tensor, X: Optional[torch.Tensor] = None, store=None,
-            slots: Optional[torch.Tensor] = None, m_ptr: Optional[torch.Tensor] = None) -> None:
+            slots: Optional[torch.Tensor] = None, m_ptr: Optional[torch.Tensor] = None,
+            lens: Optional[torch.Tensor] = None) -> None:
         """``out``: [rows] probabilities with a head, else [rows, H * directions] final states."""
+        kw = dict(X=X, store=store, slots=slots, m_ptr=m_ptr)
+        if lens is not None:
+            kw["lens"] = lens
         if not self.bidirectional:
             gp = self.packs[0]
             if self.head is not None:
-                self.launch(gp, n_rows, T, out=out, X=X, store=store, slots=slots, m_ptr=m_ptr)
+                self.launch(gp, n_rows, T, out=out, **kw)
             else:
-                self.launch(gp, n_rows, T, yh=out, X=X, store=store, slots=slots, m_ptr=m_ptr)
+                self.launch(gp, n_rows, T, yh=out, **kw)
             return
         for gp, yh in zip(self.packs, self.yh):
-            self.launch(gp, n_rows, T, yh=yh, X=X, store=store, slots=slots, m_ptr=m_ptr)
+            self.launch(gp, n_rows, T, yh=yh, **kw)
         dst = self.cat if self.head is not None else out
         torch.cat([self.yh[0][:n_rows], self.yh[1][:n_rows]], dim=1, out=dst[:n_rows])
         if self.head is not None:
@@ -175,16 +187,21 @@ class DeviceModel:
                 and os.environ.get("IGP_FUSE_TREE_ENS", "1") != "0")
 
     def run(self, X: torch.Tensor, bucket: int, m_ptr: Optional[torch.Tensor] = None,
-            ens: Optional[dict] = None) -> torch.Tensor:
+            ens: Optional[dict] = None, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
         """X: [rows, in] f32 (or [T, rows, I] for a GRU model); returns the last step's buffer.
-        ``ens`` (only when :meth:`fuses_ensemble`): K5 arguments for the fused head epilogue."""
+        ``ens`` (only when :meth:`fuses_ensemble`): K5 arguments for the fused head epilogue.
+        ``lens``: int32 [rows] sequence lengths for a plan with ``lens_input`` (None: full length)."""
         steps = self.plan.steps
         if ens is not None and not self.fuses_ensemble(bucket):
             raise ValueError("this plan cannot fuse the ensemble")
+        if lens is not None and self.gru is None:
+            raise ValueError("lens given, but the model is no sequence model")
         if self.gru is not None:
             if self.plan.steps[0].layout == 1:  # batch-major model input [rows, T, I]
                 X = X.transpose(0, 1).contiguous()
-            self.gru.run(bucket, X.shape[0], self.out, X=X, m_ptr=m_ptr)
+            if lens is not None and self.plan.lens_input is None:
+                raise ValueError("lens given, but the model has no sequence_lens input")
+            self.gru.run(bucket, X.shape[0], self.out, X=X, m_ptr=m_ptr, lens=lens)
             return self.out
         cur = X
         fused_partial = None

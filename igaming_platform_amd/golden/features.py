@@ -275,6 +275,11 @@ class GoldenFeatureStore:
                     return True
         return False
 
+    def event_count(self, account: str) -> int:
+        """Events held for the account (at most the ring)."""
+        st = self.accounts.get(account)
+        return min(len(st.events), self.cfg.event_ring) if st is not None and st.events else 0
+
     def event_history(self, account: str) -> np.ndarray:
         c = self.cfg
         out = np.zeros((c.event_ring, c.event_dim), dtype=F32)

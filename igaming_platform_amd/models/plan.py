@@ -12,7 +12,9 @@ steps:
                  the device.
 * ``DenseStep``  Gemm / MatMul(+Add) with a following Relu/Sigmoid/Tanh fused into the
                  epilogue -> K3 ``gemm`` (MFMA) or ``gemv`` (N == 1).
-* ``GRUStep``    ONNX GRU (forward / reverse / bidirectional, layout 0 / 1) -> K4 (cfg 5).
+* ``GRUStep``    ONNX GRU (forward / reverse / bidirectional, layout 0 / 1) -> K4 (cfg 5). A
+                 ``sequence_lens`` input that is an int32 graph input [N] (``Plan.lens_input``, the
+                 same for every layer; LSTM alike) lowers to masked steps: K4's masked kernels.
 * ``LSTMStep``   ONNX LSTM (same directions / layouts, default activations, no peepholes) -> K4
                  ``lstm`` (csrc/kernels/lstm.hip).
 * ``JoinStep``   Add / Concat of two branches (residual blocks, wide & deep) -> ``join``.
@@ -44,6 +46,7 @@ from ..native import native
 
 ML_DOMAIN = "ai.onnx.ml"
 POST = {0: "NONE", 1: "LOGISTIC", 2: "SOFTMAX", 3: "SOFTMAX_ZERO", 4: "PROBIT"}
+ONNX_INT32 = 6   # TensorProto.DataType of a graph input's element type
 
 
 class PlanError(RuntimeError):
@@ -171,6 +174,7 @@ class GRUStep:
     w_rev_np: Optional[np.ndarray] = None  # bidirectional: the reverse direction's W / R / B
     r_rev_np: Optional[np.ndarray] = None
     b_rev_np: Optional[np.ndarray] = None
+    masked: bool = False       # the node reads sequence_lens (Plan.lens_input): short rows hold their state
 
     @property
     def out_width(self) -> int:
@@ -180,9 +184,9 @@ class GRUStep:
         """One direction of a bidirectional layer as a unidirectional step (d = 1: reverse)."""
         if d == 0:
             return GRUStep(self.hidden, self.in_dim, self.linear_before_reset, self.w_np, self.r_np, self.b_np,
-                           seq=self.seq, layout=self.layout)
+                           seq=self.seq, layout=self.layout, masked=self.masked)
         return GRUStep(self.hidden, self.in_dim, self.linear_before_reset, self.w_rev_np, self.r_rev_np,
-                       self.b_rev_np, seq=self.seq, reverse=True, layout=self.layout)
+                       self.b_rev_np, seq=self.seq, reverse=True, layout=self.layout, masked=self.masked)
 
 
 @dataclass
@@ -202,6 +206,7 @@ class LSTMStep:
     w_rev_np: Optional[np.ndarray] = None
     r_rev_np: Optional[np.ndarray] = None
     b_rev_np: Optional[np.ndarray] = None
+    masked: bool = False       # as GRUStep.masked (h and c are held)
 
     @property
     def out_width(self) -> int:
@@ -211,9 +216,9 @@ class LSTMStep:
         """One direction of a bidirectional layer as a unidirectional step (d = 1: reverse)."""
         if d == 0:
             return LSTMStep(self.hidden, self.in_dim, self.w_np, self.r_np, self.b_np, seq=self.seq,
-                            layout=self.layout)
+                            layout=self.layout, masked=self.masked)
         return LSTMStep(self.hidden, self.in_dim, self.w_rev_np, self.r_rev_np, self.b_rev_np, seq=self.seq,
-                        reverse=True, layout=self.layout)
+                        reverse=True, layout=self.layout, masked=self.masked)
 
 
 SEQUENCE_KINDS = ("gru", "lstm")   # recurrent steps: the plan is then a sequence model
@@ -241,6 +246,8 @@ class Plan:
     seq_input: bool = False
     precision: str = "fp32"   # dense / head weights on device: fp32 (reference, f32 MFMA) | bf16
     cpu_col: Optional[int] = None  # score column in the CPU executor's output (None: ml_col)
+    # the int32 [N] graph input every GRU / LSTM layer reads as ONNX sequence_lens (None: no masking)
+    lens_input: Optional[str] = None
 
     @property
     def executor_col(self) -> int:
@@ -266,7 +273,7 @@ class Plan:
             elif s.kind == "row":
                 parts.append(f"{s.act if s.op == 'act' else s.op}({s.width})")
             else:
-                parts.append(f"{s.kind}(I={s.in_dim},H={s.hidden})")
+                parts.append(f"{s.kind}(I={s.in_dim},H={s.hidden}{',lens' if getattr(s, 'masked', False) else ''})")
         return " -> ".join(parts)
 
 
@@ -392,6 +399,26 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
     prod = {o: n for n in nodes for o in n["outputs"] if o}
     if output_name not in prod:
         raise PlanError(f"output {output_name!r} is not computed by a node")
+    # ONNX sequence_lens (input 4 of GRU / LSTM): lowered when it is a graph input typed
+    # tensor(int32) of shape [N]; that name is the one graph input allowed beside the model input
+    lens_ok = {n["inputs"][4] for n in nodes
+               if n["op_type"] in ("GRU", "LSTM") and len(n["inputs"]) > 4 and n["inputs"][4]}
+    lens_ok = {name for name in lens_ok
+               if name in inputs and name not in inits and name not in prod and name != input_name
+               and int(inputs[name][1]) == ONNX_INT32 and len(inputs[name][2]) == 1}
+    lens_seen: List[Optional[str]] = []
+
+    def seq_lens(op: str, ins) -> bool:
+        """Whether this GRU / LSTM node is masked; every layer of the chain must agree."""
+        name = ins[4] if len(ins) > 4 and ins[4] else None
+        if name is not None and name not in lens_ok:
+            raise PlanError(f"{op}: sequence_lens is lowered only as an int32 graph input of shape [N] "
+                            f"({name!r} is not)")
+        if lens_seen and lens_seen[0] != name:
+            raise PlanError(f"{op}: every layer must read the same sequence_lens input "
+                            f"({lens_seen[0]!r} and {name!r})")
+        lens_seen.append(name)
+        return name is not None
     order, live = [], set()
     stack = [(prod[output_name], 0)]
     while stack:
@@ -404,7 +431,11 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
             p = prod.get(name)
             if p is not None and id(p) not in live:
                 stack.append((p, 0))
-            elif p is None and name and name not in inits and name != input_name:
+            elif p is None and name and name not in inits and name != input_name and not (
+                    k == 4 and n["op_type"] in ("GRU", "LSTM") and name in lens_ok):
+                if k == 4 and n["op_type"] in ("GRU", "LSTM"):
+                    raise PlanError(f"{n['op_type']}: sequence_lens is lowered only as an int32 graph input of "
+                                    f"shape [N] ({name!r} is not)")
                 raise PlanError(f"the output depends on graph input {name!r} besides the model input")
             continue
         live.add(id(n))
@@ -763,8 +794,7 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
             layout = int(a.get("layout", 0))
             if direction not in ("forward", "reverse", "bidirectional") or layout not in (0, 1):
                 raise PlanError(f"GRU: direction {direction!r} / layout {layout} is not lowered")
-            if len(ins) > 4 and ins[4]:
-                raise PlanError("GRU: sequence_lens is not lowered")
+            masked = seq_lens("GRU", ins)
             if len(ins) > 5 and ins[5]:
                 raise PlanError("GRU: initial_h is not lowered (the device starts every sequence at zero)")
             if any(s.kind == "lstm" for s in steps):
@@ -787,7 +817,7 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
                                w_np=Wa[0], r_np=Ra[0], b_np=Ba[0], seq=int(seq) if seq > 0 else 0,
                                reverse=direction == "reverse", layout=layout, bidirectional=D == 2,
                                w_rev_np=Wa[1] if D == 2 else None, r_rev_np=Ra[1] if D == 2 else None,
-                               b_rev_np=Ba[1] if D == 2 else None), v.step)
+                               b_rev_np=Ba[1] if D == 2 else None, masked=masked), v.step)
             y, yh = n["outputs"][0], (n["outputs"][1] if len(n["outputs"]) > 1 else "")
             if D == 2 and y and uses.get(y, 0) > 0:
                 raise PlanError("bidirectional GRU: only the final states (Y_h) are lowered")
@@ -805,8 +835,7 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
             if direction not in ("forward", "reverse", "bidirectional") or layout not in (0, 1):
                 raise PlanError(f"LSTM: direction {direction!r} / layout {layout} is not lowered")
             D = 2 if direction == "bidirectional" else 1
-            if len(ins) > 4 and ins[4]:
-                raise PlanError("LSTM: sequence_lens is not lowered")
+            masked = seq_lens("LSTM", ins)
             if len(ins) > 5 and ins[5]:
                 raise PlanError("LSTM: initial_h is not lowered (the device starts every sequence at zero)")
             if len(ins) > 6 and ins[6]:
@@ -845,7 +874,8 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
             idx = emit(LSTMStep(hidden=H, in_dim=int(Wa.shape[2]), w_np=Wa[0], r_np=Ra[0], b_np=Ba[0],
                                 seq=int(seq) if seq > 0 else 0, reverse=direction == "reverse", layout=layout,
                                 bidirectional=D == 2, w_rev_np=Wa[1] if D == 2 else None,
-                                r_rev_np=Ra[1] if D == 2 else None, b_rev_np=Ba[1] if D == 2 else None), v.step)
+                                r_rev_np=Ra[1] if D == 2 else None, b_rev_np=Ba[1] if D == 2 else None,
+                                masked=masked), v.step)
             if D == 2 and y and uses.get(y, 0) > 0:
                 raise PlanError("bidirectional LSTM: only the final states (Y_h) are lowered")
             if y:
@@ -927,8 +957,18 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
                else "gru" if "gru" in kinds else "lstm" if "lstm" in kinds else "mlp")
     plan = Plan(family=fam, in_width=in_width, steps=steps, out_width=fv.width, ml_col=fv.ml_col,
                 metadata=dict(model.metadata), input_name=input_name, output_name=output_name,
-                seq_input=seq_input, cpu_col=fv.cpu_col)
+                seq_input=seq_input, cpu_col=fv.cpu_col, lens_input=lens_seen[0] if lens_seen else None)
     return fuse(plan) if fuse_heads else fuse(plan, heads=False)
+
+
+def sequence_lens_input(model) -> Optional[str]:
+    """The graph input a model's GRU / LSTM nodes read as ONNX sequence_lens (None: unmasked). No
+    lowering: the CPU executor paths ask this of models the device may not run."""
+    inputs = {v[0] for v in model.inputs()} - set(model.initializer_names())
+    for n in model.nodes():
+        if n["op_type"] in ("GRU", "LSTM") and len(n["inputs"]) > 4 and n["inputs"][4] in inputs:
+            return n["inputs"][4]
+    return None
 
 
 def executor_output(model, default_output: str = "output") -> Tuple[int, str]:

@@ -121,6 +121,9 @@ def ltv_mlp(n_features: int = 256, width: int = 512, layers: int = 4, seed: int 
                  metadata={"family": "mlp", "layers": str(layers), "width": str(width)})
 
 
+SEQ_LENS = "sequence_lens"   # the graph input gru() / lstm() wire to every layer with seq_lens=True
+
+
 def _gru_weights(rng, in_dim: int, hidden: int):
     s = 1.0 / np.sqrt(hidden)
     w = rng.uniform(-s, s, (1, 3 * hidden, in_dim)).astype(np.float32)
@@ -130,9 +133,12 @@ def _gru_weights(rng, in_dim: int, hidden: int):
 
 
 def gru(seq: int = 100, in_dim: int = 16, hidden: int = 256, seed: int = 5, layers: int = 2,
-        linear_before_reset: int = 1, head: bool = True, direction: str = "forward", layout: int = 0):
+        linear_before_reset: int = 1, head: bool = True, direction: str = "forward", layout: int = 0,
+        seq_lens: bool = False):
     """GRU sequence classifier. ``direction`` forward / reverse / bidirectional (one layer),
-    ``layout`` 0 ([seq, N, in]) or 1 (batch-major [N, seq, in])."""
+    ``layout`` 0 ([seq, N, in]) or 1 (batch-major [N, seq, in]). ``seq_lens``: a second graph
+    input ``sequence_lens`` (int32 [N]) wired to every layer, as a model trained on packed or padded
+    sequences exports."""
     rng = np.random.default_rng(seed)
     D = 2 if direction == "bidirectional" else 1
     if D == 2 and layers != 1:
@@ -150,7 +156,8 @@ def gru(seq: int = 100, in_dim: int = 16, hidden: int = 256, seed: int = 5, laye
         attrs["direction"] = direction
     if layout:
         attrs["layout"] = int(layout)
-    nodes = [node("GRU", ["input", "W1", "R1", "B1"], ["Y1", "Yh1"], **attrs)]
+    lens = [SEQ_LENS] if seq_lens else []
+    nodes = [node("GRU", ["input", "W1", "R1", "B1"] + lens, ["Y1", "Yh1"], **attrs)]
     # Y: layout 0 [seq, D, N, H] -> squeeze axis 1; layout 1 [N, seq, D, H] -> squeeze axis 2
     inits = [tensor("W1", w1), tensor("R1", r1), tensor("B1", b1),
              tensor("ax1", np.array([2 if layout else 1], np.int64)),
@@ -159,7 +166,7 @@ def gru(seq: int = 100, in_dim: int = 16, hidden: int = 256, seed: int = 5, laye
     if layers == 2:
         w2, r2, b2 = weights(hidden)
         nodes += [node("Squeeze", ["Y1", "ax1"], ["X2"]),
-                  node("GRU", ["X2", "W2", "R2", "B2"], ["Y2", "Yh2"], **attrs)]
+                  node("GRU", ["X2", "W2", "R2", "B2"] + lens, ["Y2", "Yh2"], **attrs)]
         inits += [tensor("W2", w2), tensor("R2", r2), tensor("B2", b2)]
         last_h = "Yh2"
     if D == 2 and not layout:  # Y_h [2, N, H] -> [N, 2, H] -> [N, 2H]
@@ -174,7 +181,8 @@ def gru(seq: int = 100, in_dim: int = 16, hidden: int = 256, seed: int = 5, laye
         nodes.append(node("Reshape", [last_h, "shp"], ["output"]))
         out_vi = value_info("output", S.FLOAT, ["N", D * hidden])
     x_dims = ["N", seq, in_dim] if layout else [seq, "N", in_dim]
-    return model(nodes, [value_info("input", S.FLOAT, x_dims)], [out_vi], inits, name="abuse_gru",
+    in_vis = [value_info("input", S.FLOAT, x_dims)] + ([value_info(SEQ_LENS, S.INT32, ["N"])] if seq_lens else [])
+    return model(nodes, in_vis, [out_vi], inits, name="abuse_gru",
                  metadata={"family": "gru", "layers": str(layers), "hidden": str(hidden), "seq": str(seq),
                            "direction": direction, "layout": str(layout)})
 
@@ -188,9 +196,10 @@ def _lstm_weights(rng, in_dim: int, hidden: int):
 
 
 def lstm(seq: int = 100, in_dim: int = 16, hidden: int = 256, seed: int = 11, layers: int = 2,
-         head: bool = True, direction: str = "forward", layout: int = 0):
+         head: bool = True, direction: str = "forward", layout: int = 0, seq_lens: bool = False):
     """LSTM sequence classifier (ONNX gate order i, o, f, c), built like :func:`gru`: ``direction``
-    forward / reverse / bidirectional (one layer), ``layout`` 0 ([seq, N, in]) or 1 ([N, seq, in])."""
+    forward / reverse / bidirectional (one layer), ``layout`` 0 ([seq, N, in]) or 1 ([N, seq, in]),
+    ``seq_lens`` the ``sequence_lens`` graph input."""
     rng = np.random.default_rng(seed)
     D = 2 if direction == "bidirectional" else 1
     if D == 2 and layers != 1:
@@ -207,7 +216,8 @@ def lstm(seq: int = 100, in_dim: int = 16, hidden: int = 256, seed: int = 11, la
         attrs["direction"] = direction
     if layout:
         attrs["layout"] = int(layout)
-    nodes = [node("LSTM", ["input", "W1", "R1", "B1"], ["Y1", "Yh1"], **attrs)]
+    lens = [SEQ_LENS] if seq_lens else []
+    nodes = [node("LSTM", ["input", "W1", "R1", "B1"] + lens, ["Y1", "Yh1"], **attrs)]
     # Y: layout 0 [seq, D, N, H] -> squeeze axis 1; layout 1 [N, seq, D, H] -> squeeze axis 2
     inits = [tensor("W1", w1), tensor("R1", r1), tensor("B1", b1),
              tensor("ax1", np.array([2 if layout else 1], np.int64)),
@@ -216,7 +226,7 @@ def lstm(seq: int = 100, in_dim: int = 16, hidden: int = 256, seed: int = 11, la
     if layers == 2:
         w2, r2, b2 = weights(hidden)
         nodes += [node("Squeeze", ["Y1", "ax1"], ["X2"]),
-                  node("LSTM", ["X2", "W2", "R2", "B2"], ["Y2", "Yh2"], **attrs)]
+                  node("LSTM", ["X2", "W2", "R2", "B2"] + lens, ["Y2", "Yh2"], **attrs)]
         inits += [tensor("W2", w2), tensor("R2", r2), tensor("B2", b2)]
         last_h = "Yh2"
     if D == 2 and not layout:  # Y_h [2, N, H] -> [N, 2, H] -> [N, 2H]
@@ -231,7 +241,8 @@ def lstm(seq: int = 100, in_dim: int = 16, hidden: int = 256, seed: int = 11, la
         nodes.append(node("Reshape", [last_h, "shp"], ["output"]))
         out_vi = value_info("output", S.FLOAT, ["N", D * hidden])
     x_dims = ["N", seq, in_dim] if layout else [seq, "N", in_dim]
-    return model(nodes, [value_info("input", S.FLOAT, x_dims)], [out_vi], inits, name="abuse_lstm",
+    in_vis = [value_info("input", S.FLOAT, x_dims)] + ([value_info(SEQ_LENS, S.INT32, ["N"])] if seq_lens else [])
+    return model(nodes, in_vis, [out_vi], inits, name="abuse_lstm",
                  metadata={"family": "lstm", "layers": str(layers), "hidden": str(hidden), "seq": str(seq),
                            "direction": direction, "layout": str(layout)})
 

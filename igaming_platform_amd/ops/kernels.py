@@ -548,14 +548,26 @@ def pack_fragments(w, k_pad: int, ks_major: bool = False) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(t).reshape(-1)).to(torch.bfloat16)
 
 
+def _pack_masked(layers, masked: Optional[bool], what: str) -> bool:
+    """The packs' ``masked`` flag: given, or what the plan steps say (all layers alike)."""
+    flags = {bool(getattr(l, "masked", False)) for l in layers}
+    if len(flags) != 1:
+        raise ValueError(f"{what}: layers must all read sequence_lens or none of them")
+    return flags.pop() if masked is None else bool(masked)
+
+
 class GruPack:
     """Device weights of a 1-2 layer GRU chain (+ optional N=1 head) for the K4 kernel."""
 
-    def __init__(self, layers, head=None, device="cuda", split: bool = False, reverse: bool = False):
+    def __init__(self, layers, head=None, device="cuda", split: bool = False, reverse: bool = False,
+                 masked: Optional[bool] = None):
         """``split``: f32-faithful mode (gru.hip layer_step_x3): each weight also as its bf16
         residual w - bf16(w); the kernel runs three MFMAs per product on (hi, lo) pairs.
         ``reverse``: ONNX direction=reverse for every layer (the kernels read the sequence last
-        step first: forward recurrences over the time-reversed input give the same states)."""
+        step first: forward recurrences over the time-reversed input give the same states).
+        ``masked``: ONNX sequence_lens (None: taken from the plan steps): a row is updated on its
+        live steps only - dense input ``lens[row]`` of them, ring input ``min(ev_count, T)`` - and
+        holds its state on the others; batch-parallel kernels only, no cluster workspace."""
         import numpy as np
         if not 1 <= len(layers) <= 2:
             raise ValueError("gru: 1 or 2 stacked layers are lowered")
@@ -568,6 +580,7 @@ class GruPack:
             raise ValueError("gru: layer 2 must be H -> H")
         if len({int(l.linear_before_reset) for l in layers}) != 1:
             raise ValueError("gru: layers must share linear_before_reset")
+        self.masked = _pack_masked(layers, masked, "gru")
         self.H, self.I, self.n_layers = H, layers[0].in_dim, len(layers)
         self.reverse = bool(reverse)
         self.waves = 0
@@ -599,7 +612,7 @@ class GruPack:
         # weight-stationary cluster kernels for 2 x 256, lbr = 1, I <= 32: bf16 (gru_ws.hip, 8
         # members per 128 / 64 rows) and, for small f32-faithful batches, the split variant
         # (gru_wsx.hip, 16 members per 32 rows; the launcher picks it up to n_cu / 4 workgroups)
-        shape_ok = self.n_layers == 2 and H == 256 and self.lbr == 1 and self.I <= 32
+        shape_ok = self.n_layers == 2 and H == 256 and self.lbr == 1 and self.I <= 32 and not self.masked
         self.ws_ok = shape_ok and not self.split
         self.wsx_ok = shape_ok and self.split
         self._ws = None
@@ -651,6 +664,19 @@ class GruPack:
             self.ws_err.zero_()
 
 
+def _masked_args(d, pack, lens, X, n_rows: int, T: int, what: str) -> None:
+    """``masked`` / ``lens`` of a K4 launch (the kernels' window word holds 16-bit time indices)."""
+    if lens is not None and (not pack.masked or X is None):
+        raise ValueError(f"{what}: lens needs a masked pack and dense input (ring input takes ev_count)")
+    if not pack.masked:
+        return
+    if T > 65535:
+        raise ValueError(f"{what}: a masked launch takes T <= 65535")
+    d["masked"] = 1
+    if lens is not None:
+        d["lens"] = _need(lens, "lens", torch.int32, n_rows, pack.device)
+
+
 # default cluster layout: 1 one 128-row cluster per CU, 3 two 64-row clusters per CU
 _GRU_WS_MODE = int(os.environ.get("IGP_GRU_WS_MODE", "3"))
 
@@ -658,8 +684,10 @@ _GRU_WS_MODE = int(os.environ.get("IGP_GRU_WS_MODE", "3"))
 def gru(gp: GruPack, n_rows: int, T: int, out: Optional[torch.Tensor] = None, yh: Optional[torch.Tensor] = None,
         X: Optional[torch.Tensor] = None, store=None, slots: Optional[torch.Tensor] = None,
         m_ptr: Optional[torch.Tensor] = None, tile_rows: int = 0, waves: int = 0, pipeline: int = 1,
-        ws: Optional[int] = None, ws_trace: Optional[torch.Tensor] = None) -> None:
+        ws: Optional[int] = None, ws_trace: Optional[torch.Tensor] = None,
+        lens: Optional[torch.Tensor] = None) -> None:
     """K4. Input either dense ``X`` f32 [T, rows, I] or the store's event rings for ``slots``.
+    ``lens`` (masked packs, dense input): int32 [rows] sequence lengths, None: every row ``T`` steps.
     ``ws``: 0 the batch-parallel kernel; 1 the weight-stationary cluster kernel when the model
     shape allows it; 2 the same with its two-half hand-off pipeline; 3 two 64-row clusters per
     CU (gru_ws2_kernel); None: IGP_GRU_WS_MODE (3)."""
@@ -671,7 +699,7 @@ def gru(gp: GruPack, n_rows: int, T: int, out: Optional[torch.Tensor] = None, yh
     d = dict(n_layers=gp.n_layers, H=gp.H, T=int(T), I=gp.I, n_rows=int(n_rows),
              m_ptr=_opt(m_ptr, "m_ptr", dtype=torch.int32, device=dev), tile_rows=int(tile_rows),
              waves=int(waves or gp.waves), pipeline=int(pipeline))
-    w = gp.workspace(n_rows) if ws else None
+    w = gp.workspace(n_rows) if ws and not gp.masked else None
     if w is not None:
         d.update(ws=int(ws), ws_clusters=w["clusters"], ws_sync=w["sync"].data_ptr(), ws_x=w["x"].data_ptr(),
                  ws_part=w["part"].data_ptr(), ws_err=gp.ws_err.data_ptr(),
@@ -682,6 +710,7 @@ def gru(gp: GruPack, n_rows: int, T: int, out: Optional[torch.Tensor] = None, yh
             d["tile_rows"] = int(gp.x3_rows)
     if gp.reverse:
         d["reverse"] = 1
+    _masked_args(d, gp, lens, X, n_rows, T, "gru")
     for i, l in enumerate(gp.layers):
         d[f"l{i}_W"] = _need(l["W"], "W", torch.bfloat16, device=dev)
         d[f"l{i}_R"] = _need(l["R"], "R", torch.bfloat16, device=dev)
@@ -720,8 +749,9 @@ class LstmPack:
     """Device weights of a 1-2 layer LSTM chain (+ optional N=1 head) for csrc/kernels/lstm.hip.
     ``layers``: models.plan.LSTMStep (w_np [4H, I], r_np [4H, H], b_np [8H], ONNX gate order)."""
 
-    def __init__(self, layers, head=None, device="cuda", split: bool = False, reverse: bool = False):
-        """``split`` / ``reverse``: as for :class:`GruPack`."""
+    def __init__(self, layers, head=None, device="cuda", split: bool = False, reverse: bool = False,
+                 masked: Optional[bool] = None):
+        """``split`` / ``reverse`` / ``masked``: as for :class:`GruPack`."""
         import numpy as np
         if not 1 <= len(layers) <= 2:
             raise ValueError("lstm: 1 or 2 stacked layers are lowered")
@@ -732,6 +762,7 @@ class LstmPack:
             raise ValueError("lstm: input dim must be a multiple of 8, <= 64")
         if len(layers) == 2 and (layers[1].hidden != H or layers[1].in_dim != H):
             raise ValueError("lstm: layer 2 must be H -> H")
+        self.masked = _pack_masked(layers, masked, "lstm")
         self.H, self.I, self.n_layers = H, layers[0].in_dim, len(layers)
         self.reverse = bool(reverse)
         dev = as_device(device)
@@ -773,9 +804,10 @@ class LstmPack:
 
 def lstm(lp: LstmPack, n_rows: int, T: int, out: Optional[torch.Tensor] = None, yh: Optional[torch.Tensor] = None,
          X: Optional[torch.Tensor] = None, store=None, slots: Optional[torch.Tensor] = None,
-         m_ptr: Optional[torch.Tensor] = None, tile_rows: int = 0) -> None:
+         m_ptr: Optional[torch.Tensor] = None, tile_rows: int = 0, lens: Optional[torch.Tensor] = None) -> None:
     """K4 (LSTM). Input either dense ``X`` f32 [T, rows, I] or the store's event rings for ``slots``;
-    writes ``out`` [rows] (a pack with a head) or ``yh`` [rows, H] (the last layer's final h)."""
+    writes ``out`` [rows] (a pack with a head) or ``yh`` [rows, H] (the last layer's final h).
+    ``lens`` (masked packs, dense input): int32 [rows] sequence lengths, None: every row ``T`` steps."""
     dev = lp.device
     if T < 1:
         raise ValueError("lstm: T must be positive")
@@ -787,6 +819,7 @@ def lstm(lp: LstmPack, n_rows: int, T: int, out: Optional[torch.Tensor] = None, 
             d["tile_rows"] = int(lp.x3_rows)
     if lp.reverse:
         d["reverse"] = 1
+    _masked_args(d, lp, lens, X, n_rows, T, "lstm")
     for i, l in enumerate(lp.layers):
         kx = l["kx_pad"]
         d[f"l{i}_W"] = _need(l["W"], "W", torch.bfloat16, 4 * lp.H * kx, dev)

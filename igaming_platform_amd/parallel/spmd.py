@@ -211,11 +211,13 @@ class ShardRunner:
                 recs[mine] = self.be.features_many(slots[mine], now)
             return self.comm.sum_i64(recs.view(np.int64).reshape(-1))
         if op == OP_EVHIST:
-            h = None
-            if aux == self.rank:
-                h = np.ascontiguousarray(self.be.event_history(aux2), np.float32)
+            # the right-aligned history and, after it, the account's event count: a model that reads
+            # sequence_lens is fed the history left-aligned with that length (engine/abuse.py)
             shape = np.asarray(hdr[5:7], np.int64)
-            buf = np.zeros(int(shape[0]) * int(shape[1]), np.float32) if h is None else h.reshape(-1)
+            buf = np.zeros(int(shape[0]) * int(shape[1]) + 1, np.float32)
+            if aux == self.rank:
+                buf[:-1] = np.ascontiguousarray(self.be.event_history(aux2), np.float32).reshape(-1)
+                buf[-1] = self.be.event_count(aux2)
             return self.comm.sum_i64(np.pad(buf, (0, len(buf) % 2)).view(np.int64))
         if op == OP_ABUSE:
             slots = np.frombuffer(payload[:4 * n], np.int32)
@@ -408,8 +410,13 @@ class SpmdGroup:
         return out.view(FEATREC).reshape(-1)[:n].copy()
 
     def event_history(self, owner: int, slot: int, shape) -> np.ndarray:
-        out = self._issue(OP_EVHIST, aux=owner, aux2=slot, extra=shape)
-        return out.view(np.float32)[: shape[0] * shape[1]].reshape(shape).copy()
+        return self.event_history_count(owner, slot, shape)[0]
+
+    def event_history_count(self, owner: int, slot: int, shape):
+        """(right-aligned history [ring, D], events held) of an account on its owner rank."""
+        out = self._issue(OP_EVHIST, aux=owner, aux2=slot, extra=shape).view(np.float32)
+        n = shape[0] * shape[1]
+        return out[:n].reshape(shape).copy(), int(out[n])
 
     def abuse_scores(self, slots, owners) -> np.ndarray:
         n = len(slots)
@@ -546,6 +553,10 @@ class ShardProxy:
     def event_history(self, slot: int) -> np.ndarray:
         shape = self.local.event_history(0).shape
         return self.g.event_history(self.o, int(slot), shape)
+
+    def event_count(self, slot: int) -> int:
+        shape = self.local.event_history(0).shape
+        return self.g.event_history_count(self.o, int(slot), shape)[1]
 
     def metrics(self):
         return None

@@ -2,7 +2,9 @@
 """K4 LSTM vs GRU timing on one box, one run: 2 x 256 layers + N=1 head, T = 100, I = 16, dense
 input, batch-parallel kernels (the GRU with linear_before_reset = 1 and its cluster kernels off),
 split (fp32 plans) and bf16 numerics. Median of --iters timed launches after --warmup.
-Prints one JSON line per variant and the LSTM / GRU time ratios."""
+Prints one JSON line per variant and the LSTM / GRU time ratios.
+--masked: each variant also as its masked (ONNX sequence_lens) instance with every length T - the
+cost of the window test and select alone - timed in rounds that alternate the two."""
 import argparse
 import json
 import os
@@ -21,6 +23,8 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--tile-rows", type=int, default=16, choices=(16, 32))
+    ap.add_argument("--masked", action="store_true", help="also time the masked instances (all lengths T), interleaved")
+    ap.add_argument("--rounds", type=int, default=4, help="--masked: alternating rounds of --iters launches each")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     import torch
@@ -40,30 +44,42 @@ def main() -> int:
         plan = compile_onnx(N.OnnxModel.from_bytes(builders.build(cell, **kw).SerializeToString()))
         layers = [s for s in plan.steps if s.kind == cell]
         for split in (True, False):
-            if cell == "gru":
-                pack = K.GruPack(layers, plan.steps[-1], dev, split=split)
-                run = lambda: K.gru(pack, a.rows, a.seq, out=out, X=X, tile_rows=a.tile_rows, ws=0)  # noqa: E731
-            else:
-                pack = K.LstmPack(layers, plan.steps[-1], dev, split=split)
-                run = lambda: K.lstm(pack, a.rows, a.seq, out=out, X=X, tile_rows=a.tile_rows)  # noqa: E731
-            for _ in range(a.warmup):
-                run()
+            def runner(masked):
+                if cell == "gru":
+                    pack = K.GruPack(layers, plan.steps[-1], dev, split=split, masked=masked)
+                    return lambda: K.gru(pack, a.rows, a.seq, out=out, X=X, tile_rows=a.tile_rows, ws=0)
+                pack = K.LstmPack(layers, plan.steps[-1], dev, split=split, masked=masked)
+                return lambda: K.lstm(pack, a.rows, a.seq, out=out, X=X, tile_rows=a.tile_rows)
+
+            def timed(run, n):
+                ts = []
+                for _ in range(n):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    run()
+                    e1.record()
+                    e1.synchronize()
+                    ts.append(e0.elapsed_time(e1))
+                return ts
+            runs = {False: runner(False)}
+            if a.masked:
+                runs[True] = runner(True)
+            for run in runs.values():
+                for _ in range(a.warmup):
+                    run()
             torch.cuda.synchronize()
-            ts = []
-            for _ in range(a.iters):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                run()
-                e1.record()
-                e1.synchronize()
-                ts.append(e0.elapsed_time(e1))
-            r = dict(cell=cell, mode="split" if split else "bf16", rows=a.rows, seq=a.seq, hidden=a.hidden,
-                     tile_rows=a.tile_rows, ms_median=float(np.median(ts)), ms_min=float(np.min(ts)),
-                     ms_max=float(np.max(ts)), seq_per_s=a.rows / float(np.median(ts)) * 1e3,
-                     finite=bool(torch.isfinite(out).all()))
-            res.append(r)
-            print(json.dumps(r), flush=True)
-    t = {(r["cell"], r["mode"]): r["ms_median"] for r in res}
+            ts = {m: [] for m in runs}
+            for _ in range(a.rounds if a.masked else 1):  # alternate the two on the same box, same process
+                for m, run in runs.items():
+                    ts[m] += timed(run, a.iters)
+            for m in runs:
+                r = dict(cell=cell, mode="split" if split else "bf16", masked=m, rows=a.rows, seq=a.seq, hidden=a.hidden,
+                         tile_rows=a.tile_rows, ms_median=float(np.median(ts[m])), ms_min=float(np.min(ts[m])),
+                         ms_max=float(np.max(ts[m])), seq_per_s=a.rows / float(np.median(ts[m])) * 1e3,
+                         finite=bool(torch.isfinite(out).all()))
+                res.append(r)
+                print(json.dumps(r), flush=True)
+    t = {(r["cell"], r["mode"]): r["ms_median"] for r in res if not r["masked"]}
     ratio = {m: t["lstm", m] / t["gru", m] for m in ("split", "bf16")}
     print(json.dumps(dict(lstm_over_gru=ratio)), flush=True)
     if a.out:
