@@ -1136,8 +1136,11 @@ __device__ __forceinline__ int hll_count_wave(const uint8_t* rg, int lane, const
 // mid-chunk: on the scorer path every event of a batch happens at the batch clock, span 0);
 // otherwise lane 0 applies them one by one. The caller stores r. `regs`: the account's HLL
 // registers in the store, or (LDSR) the wave's LDS copy that a hot account's chunks share.
-// A hot account's chunk k0 of ctot events (the scan below): a tx-ring entry or GRU event row
-// that a later event of the same batch overwrites (event k < ctot - ring size) is not written.
+// k0 / ctot: the chunk holds events k0 .. k0 + c - 1 of the account's ctot events of this batch
+// (a hot account's chunks: the scan below and the hot tail; a list segment passes neither and
+// counts as events 0 .. c - 1 of c). A tx-ring entry or GRU event row that a later event of the
+// same batch overwrites (event k < ctot - ring size) is not written: for a list segment that is
+// the event ring only, when it is shorter than the segment (c <= 64 <= ring_size).
 template <bool LDSR>
 __device__ void apply_chunk(const UpdateArgs& a, int s, AcctRT& r, int j, int c, int lane, uint8_t* regs,
                             int k0 = 0, int ctot = 0) {
@@ -1181,6 +1184,9 @@ __device__ void apply_chunk(const UpdateArgs& a, int s, AcctRT& r, int j, int c,
     return;
   }
   const int64_t amt = act ? ev.amount : 0;
+  // a list segment (no ctot): its c events are all of the account's. An event ring shorter than the
+  // segment then keeps only the last ev_ring rows; lanes writing one position would race.
+  if (ctot == 0) ctot = c;
   // tx ring: consecutive positions from the head
   if (act && k0 + lane >= ctot - a.ring_size) {
     const int pos = (r.ring_head + lane) % a.ring_size;
@@ -1357,6 +1363,8 @@ __global__ void __launch_bounds__(256) update_multi_kernel(UpdateArgs a) {
 //         the tail's (T >= ev_ring), so no per-event flags are needed.
 //   tail  the last T events (T = ev_ring rounded up to 64): exact sequential semantics through
 //         apply_chunk (new-device / new-ip flags against the registers after the bulk, GRU rows).
+// The tail list holds HOT_TAIL_MAX events; with a longer event ring T >= ev_ring cannot hold, and
+// wave 0 applies the whole account through apply_scan_chunks instead (exact at any ring length).
 // The ranks come from one ordered pass over the batch's compact row -> account column: per 512-row
 // block a ballot per wave and a 16-entry scan of the wave counts. Equal to the CPU engine's
 // sequential apply byte for byte (tests/test_engine_gpu.py hot-account tests).
@@ -1398,6 +1406,14 @@ __device__ __forceinline__ void update_hot_body(const UpdateArgs& a, int hb, int
     if (h < 0 || h >= t.cap || s < 0) continue;
     const int ctot = t.count[h];
     if (ctot <= DEDUP_LIST) continue;
+    if (a.ev && a.ev_ring > HOT_TAIL_MAX) {
+      // an event ring longer than the exact tail: bulk events of rank >= ctot - ev_ring still belong
+      // in it, with their new-device / new-ip flags. Such an account takes the exact one-wave scan
+      // (the ingestion path's apply for more than DEDUP_LIST events) instead of the bulk / tail split.
+      if (wv == 0) apply_scan_chunks(a, t, s, load_rt(a.rt + s), lane, s_regs, ctot);
+      __syncthreads();  // the LDS is the next hot account's
+      continue;
+    }
     const int Tn = min(T, ctot);
     const int Nb = ctot - Tn;  // bulk events
     AcctRT r = load_rt(a.rt + s);
