@@ -259,6 +259,9 @@ PYBIND11_MODULE(_hipk, m) {
     a.no_finish = geti(d, "no_finish", 0);
     a.all_leq = geti(d, "all_leq", 0);
     a.trace = ptr<int64_t*>(d, "trace");
+    a.sets = ptr<const uint32_t*>(d, "sets");
+    a.n_sets = geti(d, "n_sets", 0);
+    if (a.n_sets < 0 || (a.n_sets > 0 && !a.sets)) throw std::runtime_error("tree_ensemble: sets");
     return a;
   };
 
@@ -298,6 +301,9 @@ PYBIND11_MODULE(_hipk, m) {
     a.binary_class = geti(d, "binary_class", -1);
     a.all_positive = geti(d, "all_positive", 1);
     a.feat_w = geti(d, "feat_w");
+    a.sets = ptr<const uint32_t*>(d, "sets");
+    a.n_sets = geti(d, "n_sets", 0);
+    if (a.n_sets < 0 || (a.n_sets > 0 && !a.sets)) throw std::runtime_error("tree_sparse: sets");
     const int groups = geti(d, "groups", 1);
     float* partial = ptr<float*>(d, "partial");
     if (!a.X || !a.nodes || !a.roots || !a.leaf_w || !a.leaf_has || !a.out) throw std::runtime_error("tree_sparse: args");

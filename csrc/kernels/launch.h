@@ -162,6 +162,8 @@ struct TreeArgs {
   int64_t* trace;           // nullable: phase trace of sample blocks (tools/tree_bench.py)
   int32_t fuse_ens;         // grouped launch: K5 in the finish kernel's epilogue (ml = out)
   EnsembleArgs ens;
+  const uint32_t* sets;     // member-set table of the mode-6 nodes (csrc/runtime/trees.h; nullable)
+  int32_t n_sets;           // its length in 32-bit words
 };
 void launch_tree_ensemble(const TreeArgs& a, hipStream_t st);
 void launch_tree_ensemble_grouped(const TreeArgs& a, int groups, float* partial, hipStream_t st);
@@ -186,6 +188,8 @@ struct TreeSparseArgs {
   int32_t binary_class;     // -1 unless classifier binary case
   int32_t all_positive;
   int32_t feat_w;           // largest feature id + 1 (the staged X tile width)
+  const uint32_t* sets;     // member-set table of the mode-6 nodes (csrc/runtime/trees.h; nullable)
+  int32_t n_sets;           // its length in 32-bit words
 };
 void launch_tree_sparse(const TreeSparseArgs& a, int groups, float* partial, hipStream_t st);
 

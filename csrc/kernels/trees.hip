@@ -1,5 +1,6 @@
-// K2 tree_ensemble: ONNX-ML TreeEnsemble{Classifier,Regressor} on the complete-tree layout
-// (csrc/runtime/trees.h). Semantics: CPU executor (csrc/runtime/trees.cpp).
+// K2 tree_ensemble: ONNX-ML TreeEnsemble{Classifier,Regressor} and the opset-5 TreeEnsemble (with
+// its set-membership splits, tree_sets.h) on the complete-tree layout (csrc/runtime/trees.h).
+// Semantics: CPU executor (csrc/runtime/trees.cpp).
 //
 // Block = 256 threads = 4 waves, 64 samples. The block's X tile and its tree group's node table
 // (8 B/node) are staged in LDS. The tile is feature-major, [F][64]: lane r reads sample r's
@@ -17,6 +18,7 @@
 #include "head_f32.h"
 #include "launch.h"
 #include "tree_post.h"
+#include "tree_sets.h"
 
 namespace igp {
 
@@ -24,12 +26,15 @@ constexpr int TR_ROWS = 64;
 constexpr int TR_ILP = 4;
 typedef unsigned int tr_u32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ int tree_step(int i, float x, float2 nd) {
+// The general decision. Mode 6 (BRANCH_MEMBER): the threshold word is the set's offset in the
+// ensemble's set table; ensembles without such nodes pay the mode compare only.
+__device__ __forceinline__ int tree_step(int i, float x, float2 nd, const uint32_t* sets, uint32_t n_sets) {
   const uint32_t m = __float_as_uint(nd.y);
   const int mode = (m >> 16) & 7;
   const float t = nd.x;
   bool c = mode == 0 ? (x <= t) : mode == 1 ? (x < t) : mode == 2 ? (x >= t)
          : mode == 3 ? (x > t) : mode == 4 ? (x == t) : (x != t);
+  if (mode == 6) c = tree_set_member(sets, n_sets, __float_as_uint(t), x);
   c = c || (((m >> 19) & 1u) && isnan(x));
   return 2 * i + (c ? 1 : 2);
 }
@@ -62,12 +67,12 @@ __host__ __device__ __forceinline__ bool post_rowwise(const TreeArgs& a) {
 }
 
 template <bool LEQ>
-__device__ __forceinline__ int tree_next(int i, float x, float2 nd) {
+__device__ __forceinline__ int tree_next(int i, float x, float2 nd, const uint32_t* sets, uint32_t n_sets) {
   if constexpr (LEQ) {
     const bool c = x <= nd.x || (((__float_as_uint(nd.y) >> 19) & 1u) && isnan(x));
     return 2 * i + (c ? 1 : 2);
   }
-  else return tree_step(i, x, nd);
+  else return tree_step(i, x, nd, sets, n_sets);
 }
 
 // One workgroup's share of the ensemble: its 64-row tile x its tree group (blockIdx.y).
@@ -174,7 +179,7 @@ __device__ __forceinline__ void tree_block(const TreeArgs& a, int trees_per_grou
 #pragma unroll
         for (int q = 0; q < TR_ILP; ++q) xv[q] = sx[(__float_as_uint(nd[q].y) & 0xffff) * TR_ROWS + lane];
 #pragma unroll
-        for (int q = 0; q < TR_ILP; ++q) idx[q] = tree_next<LEQ>(idx[q], xv[q], nd[q]);
+        for (int q = 0; q < TR_ILP; ++q) idx[q] = tree_next<LEQ>(idx[q], xv[q], nd[q], a.sets, (uint32_t)a.n_sets);
       }
 #pragma unroll
       for (int q = 0; q < TR_ILP; ++q) {

@@ -13,6 +13,7 @@
 #include "common.h"
 #include "launch.h"
 #include "tree_post.h"
+#include "tree_sets.h"
 
 namespace igp {
 
@@ -29,10 +30,12 @@ __device__ __forceinline__ float ts_combine(int agg, float acc, float v) {
   return agg == 2 ? fminf(acc, v) : agg == 3 ? fmaxf(acc, v) : acc + v;
 }
 
-__device__ __forceinline__ bool ts_true(float x, float thr, uint32_t meta) {
+// mode 6 (BRANCH_MEMBER): the threshold word is the set's offset in the ensemble's set table
+__device__ __forceinline__ bool ts_true(float x, float thr, uint32_t meta, const uint32_t* sets, uint32_t n_sets) {
   const uint32_t mode = (meta >> 16) & 7u;
   bool c = mode == 0 ? (x <= thr) : mode == 1 ? (x < thr) : mode == 2 ? (x >= thr)
          : mode == 3 ? (x > thr) : mode == 4 ? (x == thr) : (x != thr);
+  if (mode == 6) c = tree_set_member(sets, n_sets, __float_as_uint(thr), x);
   return c || (((meta >> 19) & 1u) && isnan(x));
 }
 
@@ -113,7 +116,7 @@ __global__ void __launch_bounds__(256) tree_sparse_kernel(TreeSparseArgs a, int 
           continue;
         }
         const float x = feature((int)(meta & 0xffffu));
-        cur[j] = ts_true(x, __int_as_float(nd[j].y), meta) ? nd[j].z : nd[j].w;
+        cur[j] = ts_true(x, __int_as_float(nd[j].y), meta, a.sets, (uint32_t)a.n_sets) ? nd[j].z : nd[j].w;
         more = true;
       }
       if (!__any(more)) break;

@@ -223,6 +223,7 @@ PYBIND11_MODULE(_native, m) {
         d["k"] = e->n_targets;
         d["aggregate"] = e->aggregate;
         d["post"] = e->post;
+        d["n_member"] = e->n_member;
         return d;
       }, py::arg("node_index"))
       .def("tree_sparse", [](const exec::Executor& ex, size_t node_index) {
@@ -238,6 +239,7 @@ PYBIND11_MODULE(_native, m) {
         d["roots"] = vec_np(sp.roots);
         d["leaf_w"] = py::array_t<float>({L, int64_t(sp.k)}, sp.leaf_w.data());
         d["leaf_has"] = py::array_t<uint8_t>({L, int64_t(sp.k)}, sp.leaf_has.data());
+        d["sets"] = vec_np(sp.sets);
         d["base_values"] = vec_np(e->base_values);
         d["post"] = e->post;
         d["aggregate"] = e->aggregate;
@@ -261,6 +263,7 @@ PYBIND11_MODULE(_native, m) {
         d["k"] = c.k;
         d["nodes"] = py::array_t<float>({int64_t(c.n_trees), n_int, int64_t(2)}, c.nodes.data());
         d["leaves"] = py::array_t<float>({int64_t(c.n_trees), n_leaf, int64_t(c.k)}, c.leaves.data());
+        d["sets"] = vec_np(c.sets);
         d["base_values"] = vec_np(e->base_values);
         d["post"] = e->post;
         d["aggregate"] = e->aggregate;

@@ -479,7 +479,7 @@ Executor::Executor(onnx::Model model) : model_(std::move(model)) {
   if (order_.size() != g.nodes.size()) throw std::runtime_error("onnx: graph has unresolvable inputs or a cycle");
   for (size_t k = 0; k < g.nodes.size(); ++k) {
     const auto& op = g.nodes[k].op_type;
-    if (op == "TreeEnsembleClassifier" || op == "TreeEnsembleRegressor")
+    if (op == "TreeEnsembleClassifier" || op == "TreeEnsembleRegressor" || op == "TreeEnsemble")
       ensembles_[k] = std::make_shared<trees::Ensemble>(trees::compile(g.nodes[k]));
   }
 }
@@ -692,7 +692,7 @@ std::map<std::string, Tensor> Executor::run(const std::map<std::string, Tensor>&
         out.f[e] = x.f[src];
         for (int k2 = int(r) - 1; k2 >= 0; --k2) { if (++idx[k2] < d[k2]) break; idx[k2] = 0; }
       }
-    } else if (op == "TreeEnsembleClassifier" || op == "TreeEnsembleRegressor") {
+    } else if (op == "TreeEnsembleClassifier" || op == "TreeEnsembleRegressor" || op == "TreeEnsemble") {
       const auto* e = ensemble(k);
       const Tensor& x = get(n.inputs[0]);
       auto xf = as_float(x);

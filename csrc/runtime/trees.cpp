@@ -1,5 +1,6 @@
 // TreeEnsemble compilation and CPU evaluation (semantics: ONNX-ML TreeEnsemble{Classifier,
-// Regressor}; binary-classifier conventions follow ONNX Runtime's tree aggregator).
+// Regressor} and the opset-5 TreeEnsemble with its BRANCH_MEMBER sets; binary-classifier
+// conventions follow ONNX Runtime's tree aggregator).
 #include "trees.h"
 
 #include <algorithm>
@@ -55,6 +56,173 @@ inline bool go_true(float x, float thr, uint8_t mode, uint8_t miss) {
   return c || (miss && std::isnan(x));
 }
 
+// x == m for some member m (float equality: -0.0 matches 0.0, NaN matches nothing)
+inline bool is_member(const std::vector<float>& set, float x) {
+  auto it = std::lower_bound(set.begin(), set.end(), x);  // NaN: every m < NaN is false -> begin
+  return it != set.end() && *it == x;
+}
+
+inline bool node_true(const Ensemble& e, const GNode& g, float x) {
+  if (g.mode == MEMBER) return is_member(e.sets[g.set], x) || (g.miss && std::isnan(x));
+  return go_true(x, g.thr, g.mode, g.miss);
+}
+
+void finish_depth(Ensemble& e) {
+  for (auto& tr : e.trees) {
+    std::function<int32_t(int32_t)> depth = [&](int32_t i) -> int32_t {
+      if (tr[i].mode == LEAF) return 0;
+      return 1 + std::max(depth(tr[i].t), depth(tr[i].f));
+    };
+    e.max_depth = std::max(e.max_depth, depth(0));
+  }
+}
+
+const onnx::Tensor& tensor_attr(const onnx::Node& n, const char* name) {
+  auto a = n.attr(name);
+  if (!a || !a->t) throw std::runtime_error(std::string("TreeEnsemble: missing tensor attribute ") + name);
+  return *a->t;
+}
+
+// ai.onnx.ml opset 5: interior nodes and leaves in separate arrays, integer codes, member sets.
+// Builds what the opset-3 operators build: per tree, nodes in preorder (root, true subtree,
+// false subtree), one leaf GNode per leaf reference.
+Ensemble compile_v5(const onnx::Node& node) {
+  Ensemble e;
+  const auto& fids = ints(node, "nodes_featureids");
+  const auto& tnodes = ints(node, "nodes_truenodeids");
+  const auto& fnodes = ints(node, "nodes_falsenodeids");
+  const auto& tleaf = ints(node, "nodes_trueleafs");
+  const auto& fleaf = ints(node, "nodes_falseleafs");
+  const auto& miss = ints(node, "nodes_missing_value_tracks_true", false);
+  const auto& roots = ints(node, "tree_roots");
+  const auto& ltarget = ints(node, "leaf_targetids");
+  const onnx::Tensor& splits_t = tensor_attr(node, "nodes_splits");
+  const onnx::Tensor& modes_t = tensor_attr(node, "nodes_modes");
+  const onnx::Tensor& lw_t = tensor_attr(node, "leaf_weights");
+  if (splits_t.dtype != onnx::FLOAT || lw_t.dtype != onnx::FLOAT)
+    throw std::runtime_error("TreeEnsemble: only float nodes_splits / leaf_weights are supported");
+  if (modes_t.dtype != onnx::INT64) throw std::runtime_error("TreeEnsemble: nodes_modes must be a uint8 tensor");
+  const auto& splits = splits_t.f;
+  const auto& modes = modes_t.i;
+  const auto& lw = lw_t.f;
+  const size_t nn = fids.size(), nl = ltarget.size();
+  if (tnodes.size() != nn || fnodes.size() != nn || tleaf.size() != nn || fleaf.size() != nn ||
+      splits.size() != nn || modes.size() != nn || (!miss.empty() && miss.size() != nn))
+    throw std::runtime_error("TreeEnsemble: node attribute lengths differ");
+  if (lw.size() != nl) throw std::runtime_error("TreeEnsemble: leaf attribute lengths differ");
+  if (nn >= (size_t(1) << 31) || nl >= (size_t(1) << 31)) throw std::runtime_error("TreeEnsemble: too many nodes");
+
+  e.n_targets = int32_t(node.geti("n_targets", 1));
+  e.n_outputs = e.n_targets;
+  if (e.n_targets < 1) throw std::runtime_error("TreeEnsemble: n_targets must be positive");
+  static const int32_t agg_map[4] = {AVERAGE, SUM, MIN, MAX};
+  static const int32_t post_map[5] = {NONE, SOFTMAX, LOGISTIC, SOFTMAX_ZERO, PROBIT};
+  const int64_t agg = node.geti("aggregate_function", 1), post = node.geti("post_transform", 0);
+  if (agg < 0 || agg > 3) throw std::runtime_error("TreeEnsemble: unknown aggregate_function " + std::to_string(agg));
+  if (post < 0 || post > 4) throw std::runtime_error("TreeEnsemble: unknown post_transform " + std::to_string(post));
+  e.aggregate = agg_map[agg];
+  e.post = post_map[post];
+
+  // member sets, in the order the MEMBER nodes appear in nodes_modes, NaN-delimited
+  std::vector<int32_t> set_of(nn, -1);
+  int32_t n_member_nodes = 0;
+  for (size_t k = 0; k < nn; ++k) {
+    if (modes[k] < 0 || modes[k] > MEMBER) throw std::runtime_error("TreeEnsemble: unknown node mode " + std::to_string(modes[k]));
+    if (modes[k] == MEMBER) set_of[k] = n_member_nodes++;
+  }
+  if (auto a = node.attr("membership_values")) {
+    if (!a->t || a->t->dtype != onnx::FLOAT) throw std::runtime_error("TreeEnsemble: membership_values must be a float tensor");
+    const auto& mv = a->t->f;
+    std::vector<float> cur;
+    bool open = false;  // values (or nothing) since the last delimiter
+    auto close = [&] {
+      for (auto& v : cur) if (v == 0.f) v = 0.f;  // -0.0 -> 0.0
+      std::sort(cur.begin(), cur.end());
+      cur.erase(std::unique(cur.begin(), cur.end()), cur.end());
+      e.sets.push_back(cur);
+      cur.clear();
+    };
+    for (size_t k = 0; k < mv.size(); ++k) {
+      if (std::isnan(mv[k])) { close(); open = false; }
+      else { cur.push_back(mv[k]); open = true; }
+    }
+    if (open) close();  // no trailing NaN
+  }
+  if (int64_t(e.sets.size()) != n_member_nodes)
+    throw std::runtime_error("TreeEnsemble: membership_values holds " + std::to_string(e.sets.size()) +
+                             " sets for " + std::to_string(n_member_nodes) + " BRANCH_MEMBER nodes");
+
+  const int32_t K = e.n_targets;
+  for (size_t k = 0; k < nl; ++k)
+    if (ltarget[k] < 0 || ltarget[k] >= K) throw std::runtime_error("TreeEnsemble: leaf target id out of range");
+  auto check_ref = [&](int64_t id, bool leaf) {
+    if (id < 0 || size_t(id) >= (leaf ? nl : nn))
+      throw std::runtime_error(std::string("TreeEnsemble: ") + (leaf ? "leaf" : "node") + " id " + std::to_string(id) + " out of range");
+  };
+  for (size_t k = 0; k < nn; ++k) {
+    check_ref(tnodes[k], tleaf[k] != 0);
+    check_ref(fnodes[k], fleaf[k] != 0);
+  }
+
+  std::vector<uint8_t> seen(nn, 0);  // over all trees: a node belongs to one tree, once
+  int32_t n_leaves = 0;
+  std::vector<std::pair<int32_t, int64_t>> leaf_src;  // leaf row -> leaf id
+  e.trees.resize(roots.size());
+  for (size_t t = 0; t < roots.size(); ++t) {
+    auto& tr = e.trees[t];
+    check_ref(roots[t], false);
+    auto add_leaf = [&](int64_t id) {
+      GNode g;
+      g.leaf = n_leaves++;
+      leaf_src.emplace_back(g.leaf, id);
+      tr.push_back(g);
+      return int32_t(tr.size() - 1);
+    };
+    const int64_t r = roots[t];
+    if (tleaf[r] && fleaf[r] && tnodes[r] == fnodes[r]) {  // a tree that is one leaf
+      if (seen[r]) throw std::runtime_error("TreeEnsemble: node reachable from several roots");
+      seen[r] = 1;
+      add_leaf(tnodes[r]);
+      continue;
+    }
+    // preorder with an explicit stack: (source node or leaf id, is leaf, parent slot, true side)
+    struct Item { int64_t id; bool leaf; int32_t parent; bool side; };
+    std::vector<Item> st{{r, false, -1, true}};
+    while (!st.empty()) {
+      const Item it = st.back();
+      st.pop_back();
+      int32_t at;
+      if (it.leaf) {
+        at = add_leaf(it.id);
+      } else {
+        if (seen[it.id]) throw std::runtime_error("TreeEnsemble: cyclic tree or node reachable twice (node " + std::to_string(it.id) + ")");
+        seen[it.id] = 1;
+        GNode g;
+        g.thr = splits[it.id];
+        g.feat = int32_t(fids[it.id]);
+        if (fids[it.id] < 0 || fids[it.id] > 0x7fffffff) throw std::runtime_error("TreeEnsemble: feature id out of range");
+        g.mode = uint8_t(modes[it.id]);
+        g.miss = miss.empty() ? 0 : uint8_t(miss[it.id] != 0);
+        if (g.mode == MEMBER) { g.set = set_of[it.id]; g.thr = 0.f; ++e.n_member; }
+        e.max_feature = std::max(e.max_feature, g.feat);
+        tr.push_back(g);
+        at = int32_t(tr.size() - 1);
+        st.push_back({fnodes[it.id], fleaf[it.id] != 0, at, false});
+        st.push_back({tnodes[it.id], tleaf[it.id] != 0, at, true});
+      }
+      if (it.parent >= 0) (it.side ? tr[it.parent].t : tr[it.parent].f) = at;
+    }
+  }
+  e.leaf_w.assign(size_t(n_leaves) * K, 0.f);
+  e.leaf_has.assign(size_t(n_leaves) * K, 0);
+  for (auto& ls : leaf_src) {
+    e.leaf_w[size_t(ls.first) * K + ltarget[ls.second]] = lw[ls.second];
+    e.leaf_has[size_t(ls.first) * K + ltarget[ls.second]] = 1;
+  }
+  finish_depth(e);
+  return e;
+}
+
 
 }  // namespace
 
@@ -76,6 +244,7 @@ float erfinv(float x) {  // Giles' single-precision approximation (PROBIT post t
 }
 
 Ensemble compile(const onnx::Node& node) {
+  if (node.op_type == "TreeEnsemble") return compile_v5(node);
   Ensemble e;
   e.classifier = node.op_type == "TreeEnsembleClassifier";
   if (!e.classifier && node.op_type != "TreeEnsembleRegressor")
@@ -230,7 +399,7 @@ void eval_raw(const Ensemble& e, const float* X, int64_t n, int64_t n_feat, floa
       int32_t i = 0;
       while (tr[i].mode != LEAF) {
         const GNode& g = tr[i];
-        i = go_true(x[g.feat], g.thr, g.mode, g.miss) ? g.t : g.f;
+        i = node_true(e, g, x[g.feat]) ? g.t : g.f;
       }
       const float* w = &e.leaf_w[size_t(tr[i].leaf) * K];
       const uint8_t* h = &e.leaf_has[size_t(tr[i].leaf) * K];
@@ -312,6 +481,32 @@ uint32_t node_meta(uint32_t feat, uint32_t mode, uint32_t miss) {
   return (feat & 0xffff) | (mode << 16) | (miss << 19);
 }
 
+std::vector<uint32_t> encode_sets(const Ensemble& e, std::vector<uint32_t>& offsets) {
+  std::vector<uint32_t> tab;
+  offsets.clear();
+  for (const auto& set : e.sets) {
+    if (tab.size() + set.size() + 1 >= (size_t(1) << 31)) throw std::runtime_error("TreeEnsemble: member sets too large");
+    offsets.push_back(uint32_t(tab.size()));
+    bool bits = true;  // every member an integer in [0, SET_CAP)
+    for (float v : set) bits &= v >= 0.f && v < float(SET_CAP) && v == std::trunc(v);
+    if (bits) {
+      const uint32_t words = set.empty() ? 0 : uint32_t(set.back()) / 32 + 1;  // sorted: back() is the largest
+      tab.push_back(words);
+      const size_t at = tab.size();
+      tab.resize(at + words, 0u);
+      for (float v : set) tab[at + uint32_t(v) / 32] |= 1u << (uint32_t(v) % 32);
+    } else {
+      tab.push_back(SET_LIST | uint32_t(set.size()));
+      for (float v : set) {
+        uint32_t w;
+        std::memcpy(&w, &v, 4);
+        tab.push_back(w);
+      }
+    }
+  }
+  return tab;
+}
+
 Sparse to_sparse(const Ensemble& e) {
   Sparse sp;
   sp.depth = std::max<int32_t>(e.max_depth, 0);
@@ -322,6 +517,8 @@ Sparse to_sparse(const Ensemble& e) {
   if (total >= (size_t(1) << 31)) throw std::runtime_error("TreeEnsemble: too many nodes for 32-bit indices");
   sp.nodes.assign(total * 4, 0);
   sp.roots.resize(e.trees.size());
+  std::vector<uint32_t> set_off;
+  sp.sets = encode_sets(e, set_off);
   int32_t off = 0;
   for (size_t t = 0; t < e.trees.size(); ++t) {
     const auto& tr = e.trees[t];
@@ -336,7 +533,8 @@ Sparse to_sparse(const Ensemble& e) {
       }
       if (g.feat < 0 || g.feat > 0xffff) throw std::runtime_error("TreeEnsemble: feature id out of the device range");
       o[0] = int32_t(node_meta(uint32_t(g.feat), g.mode, g.miss));
-      std::memcpy(&o[1], &g.thr, 4);
+      if (g.mode == MEMBER) o[1] = int32_t(set_off[g.set]);
+      else std::memcpy(&o[1], &g.thr, 4);
       o[2] = off + g.t;
       o[3] = off + g.f;
     }
@@ -366,6 +564,8 @@ Complete to_complete(const Ensemble& e, int32_t max_depth_limit) {
     std::memcpy(&f, &m, 4);
     return f;
   };
+  std::vector<uint32_t> set_off;
+  c.sets = encode_sets(e, set_off);
   const float dummy_meta = meta_bits(0, LEQ, 1);
   const float inf = std::numeric_limits<float>::infinity();
   for (int32_t t = 0; t < c.n_trees; ++t) {
@@ -385,7 +585,8 @@ Complete to_complete(const Ensemble& e, int32_t max_depth_limit) {
     std::function<void(int32_t, int64_t, int32_t)> place = [&](int32_t gi, int64_t pos, int32_t d) {
       const GNode& g = tr[gi];
       if (g.mode == LEAF) { fill_leaf(pos, d, g.leaf); return; }
-      nodes[pos * 2] = g.thr;
+      if (g.mode == MEMBER) std::memcpy(&nodes[pos * 2], &set_off[g.set], 4);
+      else nodes[pos * 2] = g.thr;
       nodes[pos * 2 + 1] = meta_bits(uint32_t(g.feat), g.mode, g.miss);
       place(g.t, 2 * pos + 1, d + 1);
       place(g.f, 2 * pos + 2, d + 1);

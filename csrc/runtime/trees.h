@@ -1,4 +1,5 @@
-// TreeEnsemble{Classifier,Regressor} (ai.onnx.ml) compiled from node attributes into
+// TreeEnsemble{Classifier,Regressor} (ai.onnx.ml opset 3) and the unified TreeEnsemble operator
+// (opset 5, with set-membership splits) compiled from node attributes into
 //  (a) a general pointer layout, evaluated by the CPU executor, and
 //  (b) the implicit complete-tree layout streamed/staged by the HIP tree kernel:
 //      node i -> children 2i+1 (true) / 2i+2 (false); shallower leaves are padded by
@@ -13,7 +14,7 @@
 
 namespace igp::trees {
 
-enum Mode : uint8_t { LEQ = 0, LT = 1, GTE = 2, GT = 3, EQ = 4, NEQ = 5, LEAF = 7 };
+enum Mode : uint8_t { LEQ = 0, LT = 1, GTE = 2, GT = 3, EQ = 4, NEQ = 5, MEMBER = 6, LEAF = 7 };
 enum Aggregate : int32_t { SUM = 0, AVERAGE = 1, MIN = 2, MAX = 3 };
 enum Post : int32_t { NONE = 0, LOGISTIC = 1, SOFTMAX = 2, SOFTMAX_ZERO = 3, PROBIT = 4 };
 
@@ -24,7 +25,16 @@ struct GNode {
   uint8_t miss = 0;  // missing_value_tracks_true
   int32_t t = -1, f = -1;  // child node indices within the tree
   int32_t leaf = -1;       // leaf index into Ensemble::leaf_w (rows of K)
+  int32_t set = -1;        // MEMBER: index into Ensemble::sets
 };
+
+// Member sets on the device: one table of 32-bit words beside the nodes; a MEMBER node's
+// threshold word is the word offset of its set's header. Header = kind << 31 | length, then
+//  * kind 0, bitset: `length` words (<= SET_CAP / 32), bit v of word v / 32 set for member v.
+//    Taken by every set whose members are all integers in [0, SET_CAP) (the empty set: length 0);
+//  * kind 1, value list: `length` floats, sorted, distinct, -0.0 stored as 0.0, no NaN; bisected.
+constexpr int32_t SET_CAP = 256;
+constexpr uint32_t SET_LIST = 0x80000000u;
 
 struct Ensemble {
   bool classifier = false;
@@ -39,6 +49,8 @@ struct Ensemble {
   std::vector<std::vector<GNode>> trees;  // roots at index 0
   std::vector<float> leaf_w;              // [n_leaves][K]
   std::vector<uint8_t> leaf_has;          // [n_leaves][K]: target touched (for MIN/MAX)
+  std::vector<std::vector<float>> sets;   // member sets: sorted, distinct, -0.0 stored as 0.0
+  int32_t n_member = 0;                   // MEMBER nodes in the trees
   int32_t max_depth = 0;
   int32_t max_feature = -1;
 
@@ -61,6 +73,7 @@ struct Complete {
   int32_t k = 1;
   std::vector<float> nodes;   // [T][2^D - 1][2]: (threshold, meta bits) meta = feat | mode<<16 | miss<<19
   std::vector<float> leaves;  // [T][2^D][K]
+  std::vector<uint32_t> sets; // member-set table (empty without MEMBER nodes)
 };
 Complete to_complete(const Ensemble& e, int32_t max_depth_limit = 12);
 
@@ -75,8 +88,11 @@ struct Sparse {
   std::vector<int32_t> roots;    // [T]
   std::vector<float> leaf_w;     // [L][K]
   std::vector<uint8_t> leaf_has; // [L][K]
+  std::vector<uint32_t> sets;    // member-set table (empty without MEMBER nodes)
 };
 Sparse to_sparse(const Ensemble& e);
 uint32_t node_meta(uint32_t feat, uint32_t mode, uint32_t miss);
+// The device table of e.sets; offsets[s] = word offset of set s's header.
+std::vector<uint32_t> encode_sets(const Ensemble& e, std::vector<uint32_t>& offsets);
 
 }  // namespace igp::trees

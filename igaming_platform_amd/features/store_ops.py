@@ -110,8 +110,11 @@ def plan_importance(plan, width: int) -> Dict[str, float]:
                 feat = meta[((meta >> 16) & 7) != 7] & 0xFFFF
             else:  # complete layout: [T][2^D-1][2] f32 {thr, meta}, padding nodes have +inf thresholds
                 nodes = np.asarray(t.nodes_np, np.float32).reshape(-1, 2)
-                real = np.isfinite(nodes[:, 0])
-                feat = nodes[:, 1].view(np.uint32)[real] & 0xFFFF
+                meta = nodes[:, 1].view(np.uint32)
+                # a BRANCH_MEMBER node (mode 6) is a split on its feature: its threshold word is a
+                # set offset, whatever float those bits spell
+                real = np.isfinite(nodes[:, 0]) | (((meta >> 16) & 7) == 6)
+                feat = meta[real] & 0xFFFF
             score += np.bincount(feat.astype(np.int64), minlength=width)[:width]
     else:
         first = next((s for s in plan.steps if s.kind in ("dense", "head")), None)

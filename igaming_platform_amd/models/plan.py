@@ -4,8 +4,10 @@ The C++ reader parses the file; this module lowers the nodes the primary output 
 (one model input; chains and DAGs whose branches meet in an Add / Concat) to fused device
 steps:
 
-* ``TreeStep``   TreeEnsemble{Classifier,Regressor} (+ a following Sigmoid folded into the
-                 post transform) -> K2 ``tree_ensemble`` on the complete-tree layout, or K2b
+* ``TreeStep``   TreeEnsemble{Classifier,Regressor}, or the opset-5 TreeEnsemble with its
+                 set-membership splits (``sets``: the member-set table, checked on the host
+                 before upload), (+ a following Sigmoid folded into the post transform) -> K2
+                 ``tree_ensemble`` on the complete-tree layout, or K2b
                  ``tree_sparse`` on the pointer layout for deep (> 12) or very unbalanced trees,
                  MIN / MAX aggregates and target counts the complete kernel is not built for.
                  Every post transform (NONE, LOGISTIC, SOFTMAX, SOFTMAX_ZERO, PROBIT) runs on
@@ -73,6 +75,8 @@ class TreeStep:
     roots_np: Optional[np.ndarray] = None     # sparse: [T] root node index
     leaf_w_np: Optional[np.ndarray] = None    # sparse: [L][K]
     leaf_has_np: Optional[np.ndarray] = None  # sparse: [L][K] uint8
+    sets_np: Optional[np.ndarray] = None      # uint32 member-set table of the BRANCH_MEMBER nodes
+    sets: Any = None                          # device copy (int32 view); None when the table is empty
     nodes: Any = None
     leaves: Any = None
     base: Any = None
@@ -552,7 +556,8 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
         op, a = n["op_type"], n["attrs"]
         ins = n["inputs"]
         x = ins[0] if ins else ""
-        if op in ("TreeEnsembleClassifier", "TreeEnsembleRegressor"):
+        if op in ("TreeEnsembleClassifier", "TreeEnsembleRegressor", "TreeEnsemble"):
+            # the opset-5 TreeEnsemble compiles to the same Ensemble (no label output, no base values)
             v = plain(x, op)
             info = ex.tree_info(index[id(n)])
             if int(info["k"]) > SPARSE_MAX_K:
@@ -580,7 +585,8 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
                           classifier=bool(c["classifier"]), layout=layout, aggregate=int(c["aggregate"]),
                           roots_np=np.ascontiguousarray(c["roots"], np.int32) if sparse else None,
                           leaf_w_np=np.ascontiguousarray(c["leaf_w"], np.float32) if sparse else None,
-                          leaf_has_np=np.ascontiguousarray(c["leaf_has"], np.uint8) if sparse else None)
+                          leaf_has_np=np.ascontiguousarray(c["leaf_has"], np.uint8) if sparse else None,
+                          sets_np=np.ascontiguousarray(c["sets"], np.uint32))
             idx = emit(ts, v.step)
             if c["classifier"]:
                 col = 1 if n_out == 2 else 0
@@ -1052,6 +1058,45 @@ def _f32_padded(w: np.ndarray, n_mult: int = 128, k_mult: int = 64):
 
 PRECISIONS = ("fp32", "bf16")
 
+SET_CAP = 256            # csrc/runtime/trees.h SET_CAP: bitsets hold the integers [0, SET_CAP)
+SET_LIST = 0x80000000    # set header: kind << 31 | length
+
+
+def validate_sets(sets: Optional[np.ndarray], offsets: np.ndarray, what: str) -> None:
+    """Host check of the member-set table against the offsets its BRANCH_MEMBER nodes carry:
+    every header and every set body lies inside the table, a bitset has at most SET_CAP / 32
+    words, a value list is strictly increasing and holds no NaN. The device test then reads
+    inside the table only."""
+    tab = np.zeros(0, np.uint32) if sets is None else np.asarray(sets)
+    if tab.dtype != np.uint32 or tab.ndim != 1:
+        raise PlanError(f"{what}: the set table must be a flat uint32 array")
+    W = int(tab.size)
+    for off in np.unique(np.asarray(offsets).astype(np.int64)):
+        off = int(off)
+        if off < 0 or off >= W:
+            raise PlanError(f"{what}: set offset {off} outside the table of {W} words")
+        h = int(tab[off])
+        n = h & ~SET_LIST
+        if off + 1 + n > W:
+            raise PlanError(f"{what}: set at {off} has length {n}, past the table of {W} words")
+        if not h & SET_LIST:
+            if n * 32 > SET_CAP:
+                raise PlanError(f"{what}: bitset at {off} has {n} words (> {SET_CAP // 32})")
+            continue
+        v = tab[off + 1:off + 1 + n].view(np.float32)
+        if np.isnan(v).any():
+            raise PlanError(f"{what}: value list at {off} contains NaN")
+        if n > 1 and not (v[1:] > v[:-1]).all():
+            raise PlanError(f"{what}: value list at {off} is not sorted and distinct")
+
+
+def validate_complete(s: TreeStep) -> None:
+    """Host check of a complete-layout ensemble's member nodes (the layout itself is implicit)."""
+    nd = s.nodes_np.reshape(-1, 2).view(np.uint32)
+    member = ((nd[:, 1] >> 16) & 7) == 6
+    if member.any() or (s.sets_np is not None and s.sets_np.size):
+        validate_sets(s.sets_np, nd[member, 0], "complete trees")
+
 
 def validate_sparse(s: TreeStep) -> None:
     """Host check of a pointer-layout ensemble before it reaches the device: every child / root
@@ -1070,6 +1115,9 @@ def validate_sparse(s: TreeStep) -> None:
     ch = nodes[~leaf][:, 2:4]
     if ((ch < 0) | (ch >= N)).any():
         raise PlanError("sparse trees: child index out of range")
+    member = mode == 6
+    if member.any() or (s.sets_np is not None and s.sets_np.size):
+        validate_sets(s.sets_np, nodes[member, 1].view(np.uint32), "sparse trees")
     # initial -1: an ensemble of single-leaf trees reads no feature (max_feature = -1)
     if (nodes[~leaf, 0].view(np.uint32) & 0xFFFF).astype(np.int64).max(initial=-1) > s.max_feature:
         raise PlanError("sparse trees: feature id above max_feature")
@@ -1095,10 +1143,12 @@ def to_device(plan: Plan, device, precision: str = "fp32") -> Plan:
     pad = _f32_padded if precision == "fp32" else _bf16_padded
     for s in plan.steps:
         if s.kind == "tree":
+            (validate_sparse if s.layout == "sparse" else validate_complete)(s)  # before any upload
             s.nodes = torch.from_numpy(s.nodes_np).to(device)
             s.base = None if s.base_np is None else torch.from_numpy(s.base_np).to(device)
+            s.sets = (None if s.sets_np is None or s.sets_np.size == 0
+                      else torch.from_numpy(np.ascontiguousarray(s.sets_np, np.uint32).view(np.int32)).to(device))
             if s.layout == "sparse":
-                validate_sparse(s)
                 s.roots = torch.from_numpy(s.roots_np).to(device)
                 s.leaf_w = torch.from_numpy(s.leaf_w_np).to(device)
                 s.leaf_has = torch.from_numpy(s.leaf_has_np).to(device)

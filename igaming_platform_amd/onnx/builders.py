@@ -7,6 +7,8 @@ names. Input name ``input`` / primary output ``output`` follow ``onnx_model.go:3
 * cfg1 ``logistic``: input[N,32] -> Gemm -> Sigmoid -> output[N,1]
 * cfg2 ``gbdt``:     input[N,128] -> TreeEnsembleClassifier(100 trees, LOGISTIC)
                       -> label[N], output[N,2]
+* ``gbdt_v5``:        input[N,32] -> TreeEnsemble (ai.onnx.ml opset 5, a share of BRANCH_MEMBER
+                      nodes, LOGISTIC) -> output[N,1]
 * cfg3 ``stacked``:  input[N,128] -> TreeEnsembleRegressor(100 trees, n_targets=32)
                       -> Gemm(32x256) -> Relu -> Gemm(256x1) -> Sigmoid -> output[N,1]
 * cfg4 ``ltv_mlp``:  input[N,256] -> (Gemm -> Relu) x4 (width 512) -> Gemm -> output[N,1]
@@ -20,7 +22,7 @@ from typing import Dict
 import numpy as np
 
 from . import schema as S
-from .writer import ML_DOMAIN, model, node, tensor, tree_attrs, value_info
+from .writer import ML_DOMAIN, V5_AGGREGATE, V5_POST, model, node, tensor, tree_attrs, tree_attrs_v5, value_info
 
 MODES = ["BRANCH_LEQ", "BRANCH_LT", "BRANCH_GTE", "BRANCH_GT"]
 
@@ -76,6 +78,35 @@ def gbdt(n_trees: int = 100, depth: int = 7, n_features: int = 128, seed: int = 
                  [value_info("label", S.INT64, ["N"]), value_info("output", S.FLOAT, ["N", 2])],
                  name="fraud_gbdt",
                  metadata={"family": "gbdt", "trees": str(n_trees), "depth": str(depth)})
+
+
+def gbdt_v5(n_trees: int = 50, depth: int = 5, n_features: int = 32, seed: int = 14, member_share: float = 0.3,
+            n_categorical: int = 4, categories: int = 40, k: int = 1, post: str = "LOGISTIC"):
+    """ai.onnx.ml opset-5 ``TreeEnsemble`` with set-membership splits: random complete trees in
+    which about ``member_share`` of the nodes are ``BRANCH_MEMBER`` on one of the first
+    ``n_categorical`` columns (category codes 0 .. ``categories`` - 1; every fourth set is shifted
+    to negative codes, which the device stores as a value list instead of a bitset). Each leaf
+    writes one of the ``k`` targets. Output [N, k], ``post`` applied."""
+    rng = np.random.default_rng(seed)
+    trees = []
+    for _ in range(n_trees):
+        t = random_complete_tree(rng, depth, n_features, k, leaf_scale=0.15)
+        n_int = (1 << depth) - 1
+        keep = rng.integers(0, k, len(t["feature"]))  # one target per leaf
+        t["leaf_values"] *= (np.arange(k)[None, :] == keep[:, None])
+        t["members"] = [None] * len(t["feature"])
+        for i in np.flatnonzero(rng.random(n_int) < member_share):
+            t["feature"][i] = rng.integers(0, max(1, n_categorical))
+            t["mode"][i] = "BRANCH_MEMBER"
+            m = rng.choice(categories, size=rng.integers(1, max(2, categories // 2)), replace=False)
+            t["members"][i] = (m - categories if rng.integers(0, 4) == 0 else m).astype(np.float32)
+        trees.append(t)
+    nodes = [node("TreeEnsemble", ["input"], ["output"], domain=ML_DOMAIN, n_targets=k,
+                  aggregate_function=V5_AGGREGATE["SUM"], post_transform=V5_POST[post], **tree_attrs_v5(trees))]
+    return model(nodes, [value_info("input", S.FLOAT, ["N", n_features])],
+                 [value_info("output", S.FLOAT, ["N", k])], name="fraud_gbdt_v5", ml_opset=5,
+                 metadata={"family": "gbdt", "trees": str(n_trees), "depth": str(depth),
+                           "member_share": str(member_share)})
 
 
 def stacked(n_trees: int = 100, depth: int = 7, n_features: int = 128, k: int = 32,
@@ -434,7 +465,7 @@ def tabular_resnet(n_features: int = 32, width: int = 128, blocks: int = 2, norm
                  metadata={"family": "mlp", "blocks": str(blocks), "norm": norm})
 
 
-BUILDERS = {"logistic": logistic, "gbdt": gbdt, "stacked": stacked, "ltv_mlp": ltv_mlp, "gru": gru,
+BUILDERS = {"logistic": logistic, "gbdt": gbdt, "gbdt_v5": gbdt_v5, "stacked": stacked, "ltv_mlp": ltv_mlp, "gru": gru,
             "lstm": lstm, "torch_mlp": torch_mlp, "tabular_resnet": tabular_resnet,
             "sklearn_linear": sklearn_linear, "linear_regressor": linear_regressor,
             "mlp_classifier": mlp_classifier, "wide_deep": wide_deep, "residual_mlp": residual_mlp}

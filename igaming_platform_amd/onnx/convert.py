@@ -7,12 +7,12 @@ exported here, must score identically in the C++ executor and on the GPU.
 """
 from __future__ import annotations
 
-from typing import List
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
 from . import schema as S
-from .writer import model, node, tree_attrs, value_info
+from .writer import V5_AGGREGATE, V5_POST, model, node, tree_attrs, tree_attrs_v5, value_info
 
 
 def _tree_dict(tree, scale: float, k_index: int = 0, n_targets: int = 1):
@@ -60,3 +60,58 @@ def random_forest(est, n_features: int, input_name: str = "input", output_name: 
     return model([node("TreeEnsembleRegressor", [input_name], [output_name], domain="ai.onnx.ml", **a)],
                  [value_info(input_name, S.FLOAT, ["N", n_features])],
                  [value_info(output_name, S.FLOAT, ["N", 1])], name="sklearn_rf", metadata={"family": "gbdt"})
+
+
+def hist_gradient_boosting(est, n_features: int, input_name: str = "input", output_name: str = "output",
+                           categories: Optional[Dict[int, Sequence[float]]] = None):
+    """HistGradientBoostingRegressor / binary HistGradientBoostingClassifier -> ONNX with the
+    opset-5 ``TreeEnsemble`` operator (+ Sigmoid for the classifier: P(class 1) [N, 1]).
+
+    A numeric node is BRANCH_LEQ on ``num_threshold`` (true branch = left); a categorical node is
+    BRANCH_MEMBER on the categories set in its row of ``raw_left_cat_bitsets``;
+    ``missing_go_to_left`` becomes ``missing_value_tracks_true``. The operator has no base values:
+    the baseline prediction is added to the leaves of the first tree. Thresholds and leaf values
+    are rounded to float32.
+
+    One difference: scikit-learn sends a non-NaN category that was not among the training
+    categories the way missing values go; the operator tests membership only, so such a value
+    takes the false branch. Inputs within the training categories (and NaN) score as in sklearn.
+
+    ``categories``: feature index -> the raw input value of each ordinal code the estimator was
+    fitted on (an OrdinalEncoder in front of the estimator, folded into the member sets): the
+    exported model then reads the raw values."""
+    is_clf = hasattr(est, "classes_")
+    if is_clf and len(est.classes_) != 2:
+        raise ValueError("only binary classifiers are converted")
+    base = float(np.asarray(est._baseline_prediction).ravel()[0])
+    trees: List[dict] = []
+    for it, preds in enumerate(est._predictors):
+        p = preds[0]
+        nd, bitsets = p.nodes, p.raw_left_cat_bitsets
+        n = len(nd)
+        leaf = nd["is_leaf"].astype(bool)
+        cat = nd["is_categorical"].astype(bool) & ~leaf
+        vals = np.zeros((n, 1), np.float64)
+        vals[leaf, 0] = nd["value"][leaf] + (base if it == 0 else 0.0)
+        members = [None] * n
+        for i in np.flatnonzero(cat):
+            words = bitsets[int(nd["bitset_idx"][i])]
+            codes = [32 * w + b for w in range(len(words)) for b in range(32) if (int(words[w]) >> b) & 1]
+            raw = (categories or {}).get(int(nd["feature_idx"][i]))
+            if raw is not None:  # codes past the encoder's categories cannot occur in its output
+                codes = [raw[c] for c in codes if c < len(raw)]
+            members[i] = np.array(codes, np.float32)
+        trees.append(dict(feature=np.where(leaf, -1, nd["feature_idx"]).astype(np.int64),
+                          threshold=nd["num_threshold"].astype(np.float32),
+                          left=nd["left"].astype(np.int64), right=nd["right"].astype(np.int64),
+                          mode=["BRANCH_MEMBER" if c else "BRANCH_LEQ" for c in cat],
+                          missing_true=nd["missing_go_to_left"].astype(np.int64),
+                          leaf_values=vals.astype(np.float32), members=members))
+    a = tree_attrs_v5(trees)
+    a.update(n_targets=1, aggregate_function=V5_AGGREGATE["SUM"], post_transform=V5_POST["NONE"])
+    nodes = [node("TreeEnsemble", [input_name], ["raw" if is_clf else output_name], domain="ai.onnx.ml", **a)]
+    if is_clf:
+        nodes.append(node("Sigmoid", ["raw"], [output_name]))
+    return model(nodes, [value_info(input_name, S.FLOAT, ["N", n_features])],
+                 [value_info(output_name, S.FLOAT, ["N", 1])], name="sklearn_hgb", ml_opset=5,
+                 metadata={"family": "gbdt", "source": "sklearn"})

@@ -34,6 +34,9 @@ def attr(name: str, value):
         a.type, a.f = S.A_FLOAT, value
     elif isinstance(value, (bool, int, np.integer)):
         a.type, a.i = S.A_INT, int(value)
+    elif isinstance(value, S.TensorProto):  # tensor-valued attribute: attr(name, tensor(name, arr))
+        a.type = S.A_TENSOR
+        a.t.CopyFrom(value)
     elif isinstance(value, (str, bytes)):
         a.type, a.s = S.A_STRING, value.encode() if isinstance(value, str) else value
     elif isinstance(value, np.ndarray) and value.dtype.kind == "f":
@@ -144,3 +147,82 @@ def tree_attrs(trees: List[Dict[str, np.ndarray]], prefix: str) -> Dict[str, obj
         f"{prefix}_treeids": np.array(lt, np.int64), f"{prefix}_nodeids": np.array(ln, np.int64),
         f"{prefix}_ids": np.array(lid, np.int64), f"{prefix}_weights": np.array(lw, np.float32),
     }
+
+
+# ai.onnx.ml opset 5 TreeEnsemble integer codes
+V5_MODES = {"BRANCH_LEQ": 0, "BRANCH_LT": 1, "BRANCH_GTE": 2, "BRANCH_GT": 3, "BRANCH_EQ": 4, "BRANCH_NEQ": 5,
+            "BRANCH_MEMBER": 6}
+V5_AGGREGATE = {"AVERAGE": 0, "SUM": 1, "MIN": 2, "MAX": 3}
+V5_POST = {"NONE": 0, "SOFTMAX": 1, "LOGISTIC": 2, "SOFTMAX_ZERO": 3, "PROBIT": 4}
+
+
+def tree_attrs_v5(trees: List[Dict[str, np.ndarray]], trailing_nan: bool = True) -> Dict[str, object]:
+    """Flatten per-tree arrays into the attributes of the opset-5 ``TreeEnsemble`` operator.
+
+    The same per-tree dicts as :func:`tree_attrs`, plus ``members``: per node, the member values
+    of a ``BRANCH_MEMBER`` node (its ``threshold`` is ignored). Interior nodes and leaves go to
+    separate arrays, interior nodes in each tree's own order; a leaf row becomes one
+    (target, weight) leaf per non-zero column (column 0 when the row is all zero), so a leaf may
+    write one target only: rows with several non-zero columns are rejected. ``class_offset``
+    shifts the target id as in :func:`tree_attrs`. A tree that is a single leaf becomes a root
+    whose two branches name that leaf."""
+    fids, splits, modes, tn, fn, tl, fl, miss, roots = [], [], [], [], [], [], [], [], []
+    ltarget, lw, member = [], [], []
+    for tr in trees:
+        n = len(tr["feature"])
+        is_leaf = [tr["feature"][i] < 0 for i in range(n)]
+        node_id, leaf_id = {}, {}
+        for i in range(n):
+            if is_leaf[i]:
+                row = np.atleast_1d(np.asarray(tr["leaf_values"][i], np.float32))
+                nz = np.flatnonzero(row)
+                if len(nz) > 1:
+                    raise ValueError("TreeEnsemble (opset 5): a leaf carries one (target, weight) pair")
+                k = int(nz[0]) if len(nz) else 0
+                leaf_id[i] = len(ltarget)
+                ltarget.append(k + int(tr.get("class_offset", 0)))
+                lw.append(float(row[k]))
+            else:
+                node_id[i] = len(fids) + len(node_id)
+        if not node_id:  # a single leaf: a root with two leaf branches
+            lid = leaf_id[0]
+            roots.append(len(fids))
+            fids.append(0), splits.append(0.0), modes.append(0), miss.append(0)
+            tn.append(lid), fn.append(lid), tl.append(1), fl.append(1)
+            continue
+        children = {int(c) for i in node_id for c in (tr["left"][i], tr["right"][i])}
+        top = [i for i in range(n) if i not in children]
+        if len(top) != 1 or is_leaf[top[0]]:
+            raise ValueError("tree_attrs_v5: each tree needs exactly one root")
+        roots.append(node_id[top[0]])
+        for i in range(n):
+            if is_leaf[i]:
+                continue
+            m = tr["mode"][i]
+            fids.append(int(tr["feature"][i]))
+            modes.append(V5_MODES[m])
+            splits.append(0.0 if m == "BRANCH_MEMBER" else float(tr["threshold"][i]))
+            miss.append(int(tr["missing_true"][i]))
+            for side, ids, flags in ((tr["left"][i], tn, tl), (tr["right"][i], fn, fl)):
+                side = int(side)
+                ids.append(leaf_id[side] if is_leaf[side] else node_id[side])
+                flags.append(int(is_leaf[side]))
+            if m == "BRANCH_MEMBER":
+                member.append(np.asarray(tr["members"][i], np.float32).ravel())
+    a = {
+        "nodes_featureids": np.array(fids, np.int64),
+        "nodes_splits": tensor("nodes_splits", np.array(splits, np.float32)),
+        "nodes_modes": tensor("nodes_modes", np.array(modes, np.uint8)),
+        "nodes_truenodeids": np.array(tn, np.int64), "nodes_falsenodeids": np.array(fn, np.int64),
+        "nodes_trueleafs": np.array(tl, np.int64), "nodes_falseleafs": np.array(fl, np.int64),
+        "nodes_missing_value_tracks_true": np.array(miss, np.int64),
+        "tree_roots": np.array(roots, np.int64),
+        "leaf_targetids": np.array(ltarget, np.int64),
+        "leaf_weights": tensor("leaf_weights", np.array(lw, np.float32)),
+    }
+    if member:
+        nan = np.array([np.nan], np.float32)
+        parts = [p for m in member for p in (m, nan)]
+        mv = np.concatenate(parts if trailing_nan else parts[:-1])
+        a["membership_values"] = tensor("membership_values", mv.astype(np.float32))
+    return a

@@ -223,6 +223,15 @@ def update_segments(store, cfg_dev: torch.Tensor, req: torch.Tensor, n_max: int,
 
 
 # --------------------------------------------------------------------------- K2
+def _tree_sets(tp, dev) -> dict:
+    """The member-set table of the step's BRANCH_MEMBER nodes (int32 view of the uint32 words,
+    validated by models.plan at upload); absent or empty: no such nodes."""
+    sets = getattr(tp, "sets", None)
+    if sets is None or sets.numel() == 0:
+        return dict(sets=None, n_sets=0)
+    return dict(sets=_need(sets, "sets", torch.int32, device=dev), n_sets=int(sets.numel()))
+
+
 def _tree_dict(tp, X: torch.Tensor, out: Optional[torch.Tensor], n_rows: int, partial, groups: int,
                no_finish: bool, trace, ens) -> dict:
     dev = X.device
@@ -246,6 +255,7 @@ def _tree_dict(tp, X: torch.Tensor, out: Optional[torch.Tensor], n_rows: int, pa
         average=tp.average, binary_class=tp.binary_class, all_positive=tp.all_positive,
         groups=int(groups), partial=_opt(partial, "partial", dtype=torch.float32), no_finish=int(no_finish),
         all_leq=int(tp.all_leq), trace=_opt(trace, "trace", dtype=torch.int64, min_numel=64), ens=ens,
+        **_tree_sets(tp, dev),
     )
     if tp.nodes.numel() < tp.n_trees * ((1 << tp.depth) - 1) * 2:
         raise ValueError("node table smaller than n_trees * (2^depth - 1)")
@@ -312,7 +322,7 @@ def tree_sparse(tp, X: torch.Tensor, out: torch.Tensor, n_rows: int, partial: Op
              n_rows=int(n_rows), n_trees=tp.n_trees, depth=tp.depth, k=tp.k, n_out=tp.n_out, post=tp.post,
              aggregate=tp.aggregate, binary_class=tp.binary_class, all_positive=tp.all_positive,
              feat_w=int(max(tp.max_feature, 0) + 1), groups=int(groups),
-             partial=_opt(partial, "partial", dtype=torch.float32))
+             partial=_opt(partial, "partial", dtype=torch.float32), **_tree_sets(tp, dev))
     if out.dim() == 2 and out.shape[1] != tp.n_out:
         raise ValueError("out must have n_out columns")
     _mod().tree_sparse(d, _stream())

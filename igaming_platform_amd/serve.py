@@ -25,7 +25,7 @@ def _fraud_model(a, cfg: Config):
     if not a.synthetic_model:
         return None
     from .onnx import builders
-    kw = {"n_features": cfg.features.width} if a.synthetic_model == "logistic" else {}
+    kw = {"n_features": cfg.features.width} if a.synthetic_model in ("logistic", "gbdt_v5") else {}
     return builders.build(a.synthetic_model, **kw).SerializeToString()
 
 

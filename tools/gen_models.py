@@ -15,6 +15,8 @@ MODELS = {
     "cfg3_stacked.onnx": ("stacked", dict(n_trees=100, depth=7, n_features=128, k=32)),
     "cfg4_ltv_mlp.onnx": ("ltv_mlp", dict(n_features=256, width=512, layers=4)),
     "cfg5_abuse_gru.onnx": ("gru", dict(seq=100, in_dim=16, hidden=256)),
+    # ai.onnx.ml opset 5: the unified TreeEnsemble operator with set-membership (categorical) splits
+    "gbdt_v5_member.onnx": ("gbdt_v5", dict(n_trees=50, depth=5, n_features=32, member_share=0.3)),
     # framework-style exports: BatchNormalization / Dropout / Softmax, and the residual tabular net
     "torch_mlp.onnx": ("torch_mlp", dict(n_features=32, hidden=64, layers=2, act="Relu", out=2)),
     "tabular_resnet.onnx": ("tabular_resnet", dict(n_features=32, width=128, blocks=2, norm="layer")),
