@@ -11,9 +11,10 @@
 // ht computes the same (row, unit) every step, so z/r/h~ combine lane-locally.
 // Layer 2 consumes layer 1's h_t straight from LDS (Y never touches HBM). The layer-1 input
 // of step t+1 is prefetched into registers during step t (from the HBM event ring, mode 1,
-// or a dense [T][B][I] tensor, mode 0).
+// or a dense [T][B][I] tensor, mode 0) by seq_input.h, shared with lstm.hip and the cluster kernels.
 #include "common.h"
 #include "launch.h"
+#include "seq_input.h"
 #include "seq_window.h"
 
 namespace igp {
@@ -202,11 +203,6 @@ __device__ __forceinline__ void layer_step(const WFrag& gW, const WFrag& gR, con
 // three MFMAs (lo*hi + hi*lo + hi*hi; lo*lo ~2^-18 relative is dropped) into f32 accumulators,
 // and the hidden state stays f32 in registers. ~1e-5 relative to fp32 at 3x the bf16 MFMA
 // count; the f32 MFMA (v_mfma_f32_16x16x4_f32) would be ~16x slower than bf16.
-__device__ __forceinline__ void gru_split(float x, uint16_t& hi, uint16_t& lo) {
-  hi = f32_to_bf16(x);
-  lo = f32_to_bf16(x - __uint_as_float((uint32_t)hi << 16));
-}
-
 #define GRU_MMA3(acc, ah, al, bh, bl)                                      \
   do {                                                                     \
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, acc, 0, 0, 0);   \
@@ -282,11 +278,11 @@ __device__ __forceinline__ void layer_step_x3(const WFrag& gW, const WFrag& gWl,
           float h = (1.f - z) * hh + z * hs[i][rt][r];
           if constexpr (MASKED != 0) h = live(rt, r) ? h : hs[i][rt][r];
           hs[i][rt][r] = h;
-          gru_split(h, hnext[o], hnextl[o]);
+          bf16_split(h, hnext[o], hnextl[o]);
         } else {
           zk[i][rt][r] = z;
           xk[i][rt][r] = ax[rt][r];
-          gru_split(rr * hs[i][rt][r], rb[o], rbl[o]);
+          bf16_split(rr * hs[i][rt][r], rb[o], rbl[o]);
         }
       }
   }
@@ -320,7 +316,7 @@ __device__ __forceinline__ void layer_step_x3(const WFrag& gW, const WFrag& gWl,
           if constexpr (MASKED != 0) h = live(rt, r) ? h : hs[i][rt][r];
           hs[i][rt][r] = h;
           const int o = (rt * 16 + crow + r) * HS + j;
-          gru_split(h, hnext[o], hnextl[o]);
+          bf16_split(h, hnext[o], hnextl[o]);
         }
     }
   }
@@ -419,49 +415,16 @@ __global__ void __launch_bounds__(NW * 64) gru_kernel(GruArgs a) {
     for (int i = tid; i < 6 * H; i += NT) bias[6 * H + i] = a.layer[1].bias[i];
 
   // ---- layer-1 input staging: thread -> (row rr, 8-element chunk c), fixed for all t
-  const int I = a.I;
-  const int chunks = I >> 3;
+  const int chunks = a.I >> 3;
   const int my_rr = tid / max(chunks, 1), my_c = tid - my_rr * max(chunks, 1);
   const bool stager = chunks > 0 && my_rr < M;
   const int grow = row0 + my_rr;
-  int slot = -1, head = 0, valid_from = a.T;
-  if (stager && grow < n_live) {
-    if (a.mode == 1) {
-      slot = a.slots[grow];
-      if (slot >= 0) {
-        const AcctRT r = a.rt[slot];
-        const int cnt = min(r.ev_count, a.T);
-        head = r.ev_head;
-        valid_from = a.T - cnt;
-      }
-    } else {
-      valid_from = 0;
-    }
-  }
-  auto load_x = [&](int t) -> uint4 {
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (a.reverse) t = a.T - 1 - t;  // direction=reverse: forward over the time-reversed sequence
-    if (!stager || t < valid_from || t < 0) return v;
-    if (a.mode == 1) {
-      int idx = (head - a.T + t) % a.ev_ring;
-      if (idx < 0) idx += a.ev_ring;
-      v = *reinterpret_cast<const uint4*>(a.ev + (((size_t)slot * a.ev_ring + idx) * I + my_c * 8));
-    } else {
-      const float* src = a.X + (((size_t)t * a.x_rows + grow) * I + my_c * 8);
-      const float4 f0 = *reinterpret_cast<const float4*>(src);
-      const float4 f1 = *reinterpret_cast<const float4*>(src + 4);
-      v.x = (uint32_t)f32_to_bf16(f0.x) | ((uint32_t)f32_to_bf16(f0.y) << 16);
-      v.y = (uint32_t)f32_to_bf16(f0.z) | ((uint32_t)f32_to_bf16(f0.w) << 16);
-      v.z = (uint32_t)f32_to_bf16(f1.x) | ((uint32_t)f32_to_bf16(f1.y) << 16);
-      v.w = (uint32_t)f32_to_bf16(f1.z) | ((uint32_t)f32_to_bf16(f1.w) << 16);
-    }
-    return v;
-  };
+  const SeqSrc src = stager ? seq_src(a, grow, n_live) : SeqSrc{-1, 0, a.T};
   if constexpr (MASKED != 0) {
-    if (stager && my_c == 0) reinterpret_cast<uint32_t*>(red + NW * M)[my_rr] = seq_window(a, grow, n_live, valid_from);
+    if (stager && my_c == 0) reinterpret_cast<uint32_t*>(red + NW * M)[my_rr] = seq_window(a, grow, n_live, src.from);
   }
   __syncthreads();  // zeroing done before the first staged row lands
-  if (stager) *reinterpret_cast<uint4*>(XB(0) + my_rr * XS + my_c * 8) = load_x(0);
+  if (stager) *reinterpret_cast<uint4*>(XB(0) + my_rr * XS + my_c * 8) = seq_load(a, src, grow, my_c, 0);
 
   float hs0[HTW][RT][4], hs1[HTW][RT][4];
 #pragma unroll
@@ -477,7 +440,7 @@ __global__ void __launch_bounds__(NW * 64) gru_kernel(GruArgs a) {
     SeqLive<MASKED> live;
     if constexpr (MASKED != 0)
       live = {reinterpret_cast<const uint32_t*>(red + NW * M), (lane >> 4) * 4, a.reverse ? a.T - 1 - t : t};
-    const uint4 xn = (t + 1 < a.T) ? load_x(t + 1) : make_uint4(0, 0, 0, 0);
+    const uint4 xn = seq_load(a, src, grow, my_c, t + 1);
     layer_step<RT, KSX, KSH, LBR, NW, MASKED>(w0, r0, bias, XB(pb), XS, HB(0, pb), HB(0, nb), rb, hs0, lane, wave,
                                               live);
     __syncthreads();
@@ -539,52 +502,18 @@ __global__ void __launch_bounds__(NW * 64) gru_x3_kernel(GruArgs a) {
   if (a.n_layers == 2)
     for (int i = tid; i < 6 * H; i += NT) bias[6 * H + i] = a.layer[1].bias[i];
 
-  const int I = a.I;
-  const int chunks = I >> 3;
+  const int chunks = a.I >> 3;
   const int my_rr = tid / max(chunks, 1), my_c = tid - my_rr * max(chunks, 1);
   const bool stager = chunks > 0 && my_rr < M;
   const int grow = row0 + my_rr;
-  int slot = -1, head = 0, valid_from = a.T;
-  if (stager && grow < n_live) {
-    if (a.mode == 1) {
-      slot = a.slots[grow];
-      if (slot >= 0) {
-        const AcctRT r = a.rt[slot];
-        head = r.ev_head;
-        valid_from = a.T - min(r.ev_count, a.T);
-      }
-    } else {
-      valid_from = 0;
-    }
-  }
-  // x_t as (hi, lo) bf16 halves: the event ring holds bf16 values (lo = 0); dense f32 input splits
-  auto load_x = [&](int t, uint4& hi, uint4& lo) {
-    hi = lo = make_uint4(0, 0, 0, 0);
-    if (t >= a.T) return;
-    if (a.reverse) t = a.T - 1 - t;
-    if (!stager || t < valid_from) return;
-    if (a.mode == 1) {
-      int idx = (head - a.T + t) % a.ev_ring;
-      if (idx < 0) idx += a.ev_ring;
-      hi = *reinterpret_cast<const uint4*>(a.ev + (((size_t)slot * a.ev_ring + idx) * I + my_c * 8));
-    } else {
-      const float* src = a.X + (((size_t)t * a.x_rows + grow) * I + my_c * 8);
-      uint16_t h8[8], l8[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) gru_split(src[e], h8[e], l8[e]);
-      hi = make_uint4(h8[0] | (uint32_t)h8[1] << 16, h8[2] | (uint32_t)h8[3] << 16, h8[4] | (uint32_t)h8[5] << 16,
-                      h8[6] | (uint32_t)h8[7] << 16);
-      lo = make_uint4(l8[0] | (uint32_t)l8[1] << 16, l8[2] | (uint32_t)l8[3] << 16, l8[4] | (uint32_t)l8[5] << 16,
-                      l8[6] | (uint32_t)l8[7] << 16);
-    }
-  };
+  const SeqSrc src = stager ? seq_src(a, grow, n_live) : SeqSrc{-1, 0, a.T};
   if constexpr (MASKED != 0) {
-    if (stager && my_c == 0) reinterpret_cast<uint32_t*>(red + NW * M)[my_rr] = seq_window(a, grow, n_live, valid_from);
+    if (stager && my_c == 0) reinterpret_cast<uint32_t*>(red + NW * M)[my_rr] = seq_window(a, grow, n_live, src.from);
   }
   __syncthreads();
   if (stager) {
     uint4 h, l;
-    load_x(0, h, l);
+    seq_load_split(a, src, grow, my_c, 0, h, l);
     *reinterpret_cast<uint4*>(XB(0, 0) + my_rr * XS + my_c * 8) = h;
     *reinterpret_cast<uint4*>(XB(1, 0) + my_rr * XS + my_c * 8) = l;
   }
@@ -603,7 +532,7 @@ __global__ void __launch_bounds__(NW * 64) gru_x3_kernel(GruArgs a) {
     if constexpr (MASKED != 0)
       live = {reinterpret_cast<const uint32_t*>(red + NW * M), (lane >> 4) * 4, a.reverse ? a.T - 1 - t : t};
     uint4 xh, xl;
-    load_x(t + 1, xh, xl);
+    seq_load_split(a, src, grow, my_c, t + 1, xh, xl);
     layer_step_x3<RT, KSX, KSH, LBR, NW, MASKED>(w0, w0l, r0, r0l, bias, XB(0, pb), XB(1, pb), XS, HB(0, 0, pb),
                                                  HB(1, 0, pb), HB(0, 0, nb), HB(1, 0, nb), rb, rb + M * HS, hs0, lane,
                                                  wave, live);
@@ -714,49 +643,16 @@ __global__ void __launch_bounds__(NW * 64) gru2_pipe_kernel(GruArgs a) {
     bias[i] = a.layer[0].bias[i];
     bias[6 * H + i] = a.layer[1].bias[i];
   }
-  const int I = a.I;
-  const int chunks = I >> 3;
+  const int chunks = a.I >> 3;
   const int my_rr = tid / max(chunks, 1), my_c = tid - my_rr * max(chunks, 1);
   const bool stager = chunks > 0 && my_rr < M;
   const int grow = row0 + my_rr;
-  int slot = -1, head = 0, valid_from = a.T;
-  if (stager && grow < n_live) {
-    if (a.mode == 1) {
-      slot = a.slots[grow];
-      if (slot >= 0) {
-        const AcctRT r = a.rt[slot];
-        head = r.ev_head;
-        valid_from = a.T - min(r.ev_count, a.T);
-      }
-    } else {
-      valid_from = 0;
-    }
-  }
-  auto load_x = [&](int t) -> uint4 {
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (t >= a.T) return v;
-    if (a.reverse) t = a.T - 1 - t;
-    if (!stager || t < valid_from) return v;
-    if (a.mode == 1) {
-      int idx = (head - a.T + t) % a.ev_ring;
-      if (idx < 0) idx += a.ev_ring;
-      v = *reinterpret_cast<const uint4*>(a.ev + (((size_t)slot * a.ev_ring + idx) * I + my_c * 8));
-    } else {
-      const float* src = a.X + (((size_t)t * a.x_rows + grow) * I + my_c * 8);
-      const float4 f0 = *reinterpret_cast<const float4*>(src);
-      const float4 f1 = *reinterpret_cast<const float4*>(src + 4);
-      v.x = (uint32_t)f32_to_bf16(f0.x) | ((uint32_t)f32_to_bf16(f0.y) << 16);
-      v.y = (uint32_t)f32_to_bf16(f0.z) | ((uint32_t)f32_to_bf16(f0.w) << 16);
-      v.z = (uint32_t)f32_to_bf16(f1.x) | ((uint32_t)f32_to_bf16(f1.y) << 16);
-      v.w = (uint32_t)f32_to_bf16(f1.z) | ((uint32_t)f32_to_bf16(f1.w) << 16);
-    }
-    return v;
-  };
+  const SeqSrc src = stager ? seq_src(a, grow, n_live) : SeqSrc{-1, 0, a.T};
   if constexpr (MASKED != 0) {
-    if (stager && my_c == 0) reinterpret_cast<uint32_t*>(red + NW * M)[my_rr] = seq_window(a, grow, n_live, valid_from);
+    if (stager && my_c == 0) reinterpret_cast<uint32_t*>(red + NW * M)[my_rr] = seq_window(a, grow, n_live, src.from);
   }
   __syncthreads();
-  if (stager) *reinterpret_cast<uint4*>(XB(0) + my_rr * XS + my_c * 8) = load_x(0);
+  if (stager) *reinterpret_cast<uint4*>(XB(0) + my_rr * XS + my_c * 8) = seq_load(a, src, grow, my_c, 0);
   float hs[HTW][RT][4];
 #pragma unroll
   for (int i = 0; i < HTW; ++i)
@@ -767,7 +663,7 @@ __global__ void __launch_bounds__(NW * 64) gru2_pipe_kernel(GruArgs a) {
   __syncthreads();
 
   for (int t = 0; t <= a.T; ++t) {
-    const uint4 xn = load_x(t + 1);
+    const uint4 xn = seq_load(a, src, grow, my_c, t + 1);
     // each half tests the window against its own step: layer 1 is at t, layer 2 at t - 1
     SeqLive<MASKED> live;
     if constexpr (MASKED != 0) {

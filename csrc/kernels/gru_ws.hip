@@ -26,42 +26,51 @@
 //
 // The f32 hidden state never leaves registers (lane-local z/r/h~ combine, as in gru.hip); the
 // head is a fixed-order sum of per-member f32 partials (deterministic).
-#include "common.h"
-#include "launch.h"
+//
+// Input staging comes from seq_input.h; the protocol pieces around the recurrence (counter waits,
+// NaN pre-fill, final arrival, ...) are shared with gru_wsx.hip through gru_cluster.h.
+#include <type_traits>
+
+#include "gru_cluster.h"
 
 namespace igp {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-
 constexpr int WS_CL = 8;              // workgroups per cluster
 constexpr int WS_M = 128;             // sequences per cluster
 constexpr int WS_RT = WS_M / 16;      // MFMA row tiles
-constexpr int WS_H = 256;
+constexpr int WS_H = kClusterH;
 constexpr int WS_HT = WS_H / 16;      // hidden tiles
 constexpr int WS_HS = WS_H + 8;       // LDS row stride (bf16), conflict-free A-fragment reads
 constexpr int WS_XS = 32 + 8;
 constexpr int WS_UW = WS_H / WS_CL;   // hidden units per member (32)
 constexpr int WS_SLICE = 2 * WS_M * WS_UW;  // bf16 per member slice (both layers)
 constexpr int WS_CH = WS_SLICE / 8;   // 16-B chunks per slice (1024)
-constexpr uint64_t WS_WAIT_TICKS = 20000000;  // 200 ms of wall_clock64 (100 MHz): never hang the GPU
-constexpr int SC1 = 16;               // buffer aux bit: sc1 (L2-coherent, bypasses L1)
-
-// v_exp_f32 + v_rcp_f32 (1 ulp): the IEEE divide sequence would cost ~10 VALU per gate
-__device__ __forceinline__ float sig_(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
-__device__ __forceinline__ float tanh_(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(__expf(2.f * x) + 1.f); }
 
 __device__ __forceinline__ bf16x8 lds_frag(const uint16_t* base, int stride, int row, int k) {
   const uint4 v = *reinterpret_cast<const uint4*>(base + row * stride + k);
   return __builtin_bit_cast(bf16x8, v);
 }
 
-// packed fragment (nt, ks) of a [N/16][KS][64][8] bf16 weight (ops/kernels.py pack_fragments)
-__device__ __forceinline__ bf16x8 wfrag(const uint16_t* p, int nt, int KS, int ks, int lane) {
-  const uint4 v = *reinterpret_cast<const uint4*>(p + (((size_t)nt * KS + ks) * 64 + lane) * 8);
-  return __builtin_bit_cast(bf16x8, v);
+// this wave's B fragments of hidden tile ht, three gates, -> registers (stationary for the whole
+// launch). L = 0: x part 1 + h part 8 k-steps; L = 1: 8 + 8.
+template <int L>
+__device__ __forceinline__ void ws_load_weights(const GruArgs& a, int ht, int lane, bf16x8 (&wz)[16],
+                                                bf16x8 (&wr)[16], bf16x8 (&wh)[16]) {
+  const uint16_t* W = a.layer[L].W;
+  const uint16_t* R = a.layer[L].R;
+  constexpr int NX = L == 0 ? 1 : 8;  // k-steps of the input part
+#pragma unroll
+  for (int ks = 0; ks < 8; ++ks) {
+    if (ks < NX) {
+      wz[ks] = cluster_wfrag(W, ht, NX, ks, lane);
+      wr[ks] = cluster_wfrag(W, WS_HT + ht, NX, ks, lane);
+      wh[ks] = cluster_wfrag(W, 2 * WS_HT + ht, NX, ks, lane);
+    }
+    wz[NX + ks] = cluster_wfrag(R, ht, 8, ks, lane);
+    wr[NX + ks] = cluster_wfrag(R, WS_HT + ht, 8, ks, lane);
+    wh[NX + ks] = cluster_wfrag(R, 2 * WS_HT + ht, 8, ks, lane);
+  }
 }
 
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
@@ -120,12 +129,8 @@ __device__ __forceinline__ void ws_epilogue(const f32x4 (&acc)[4][2], float (&hs
 #pragma unroll
   for (int u = 0; u < 2; ++u)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float z = sig_(acc[0][u][r] + bv[0]);
-      const float rr = sig_(acc[1][u][r] + bv[1]);
-      const float hh = tanh_(acc[2][u][r] + bv[2] + rr * (acc[3][u][r] + bv[3]));
-      hs[rt0 + u][r] = (1.f - z) * hh + z * hs[rt0 + u][r];
-    }
+    for (int r = 0; r < 4; ++r)
+      hs[rt0 + u][r] = cluster_gate(acc[0][u][r], acc[1][u][r], acc[2][u][r], acc[3][u][r], bv, hs[rt0 + u][r]);
 }
 
 // row tiles [RT0, RT0 + NRT) of one layer's step (NRT even)
@@ -143,24 +148,6 @@ __device__ __forceinline__ void ws_layer(const bf16x8 (&wz)[16], const bf16x8 (&
   ws_epilogue(acc[(NRT / 2 - 1) & 1], hs, bv, RT0 + NRT - 2);
 }
 #undef MFMA
-
-// bounded poll of a cluster counter by one lane; returns false on timeout, after poisoning both
-// counters of the cluster (`base`: cnt[0] and cnt[8], gru.hip kClusterPoison) so that no member
-// still to arrive and no launch queued behind this one passes a wait on a part-advanced count
-__device__ __forceinline__ bool ws_wait(int32_t* cnt, int target, int32_t* base) {
-  const uint64_t t0 = wall_clock64();
-  for (;;) {
-    for (int n = 0; n < 64; ++n) {
-      if (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= target) return true;
-      __builtin_amdgcn_s_sleep(1);
-    }
-    if (wall_clock64() - t0 > WS_WAIT_TICKS) {
-      __hip_atomic_exchange(base, kClusterPoison, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_exchange(base + 8, kClusterPoison, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return false;
-    }
-  }
-}
 
 // SPLIT: the cluster's 128 sequences as two independent 64-row halves in a software pipeline
 // (GruArgs.ws == 2): the hand-off of one half (sc1 stores draining, counter, gather) runs beside
@@ -190,50 +177,13 @@ __global__ void __launch_bounds__(256, 1) gru_ws_kernel(GruArgs a) {
   const int j = ht * 16 + ccol;            // this lane's hidden unit
   const int T = a.T;
   int32_t* const cnt = a.ws_sync + cl * 16;
-  // outputs start as NaN: a cluster that gives up (bounded wait) leaves them so, and the host
-  // detects it (AbuseGpu.wait) instead of reading the previous batch's values
-  if (a.head_w && mem == 0 && tid < WS_M && row0 + tid < n_live) a.out[row0 + tid] = __builtin_nanf("");
-  if (a.yh)
-    for (int e = tid; e < WS_M * WS_UW; e += 256) {
-      const int row = row0 + e / WS_UW;
-      if (row < n_live) a.yh[(size_t)row * WS_H + mem * WS_UW + e % WS_UW] = __builtin_nanf("");
-    }
+  cluster_nan_fill<WS_M, WS_UW>(a, row0, n_live, mem, tid);
 
-  // ---- weights -> registers (stationary for the whole launch)
   bf16x8 wz[16], wr[16], wh[16];
-  if (layer == 0) {
-    const uint16_t* W = a.layer[0].W;
-    const uint16_t* R = a.layer[0].R;
-    wz[0] = wfrag(W, ht, 1, 0, lane);
-    wr[0] = wfrag(W, WS_HT + ht, 1, 0, lane);
-    wh[0] = wfrag(W, 2 * WS_HT + ht, 1, 0, lane);
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-      wz[1 + ks] = wfrag(R, ht, 8, ks, lane);
-      wr[1 + ks] = wfrag(R, WS_HT + ht, 8, ks, lane);
-      wh[1 + ks] = wfrag(R, 2 * WS_HT + ht, 8, ks, lane);
-    }
-  } else {
-    const uint16_t* W = a.layer[1].W;
-    const uint16_t* R = a.layer[1].R;
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-      wz[ks] = wfrag(W, ht, 8, ks, lane);
-      wr[ks] = wfrag(W, WS_HT + ht, 8, ks, lane);
-      wh[ks] = wfrag(W, 2 * WS_HT + ht, 8, ks, lane);
-      wz[8 + ks] = wfrag(R, ht, 8, ks, lane);
-      wr[8 + ks] = wfrag(R, WS_HT + ht, 8, ks, lane);
-      wh[8 + ks] = wfrag(R, 2 * WS_HT + ht, 8, ks, lane);
-    }
-  }
+  if (layer == 0) ws_load_weights<0>(a, ht, lane, wz, wr, wh);
+  else ws_load_weights<1>(a, ht, lane, wz, wr, wh);
   float bv[4];
-  {
-    const float* bs = a.layer[layer].bias;  // Wb z,r,h | Rb z,r,h
-    bv[0] = bs[j] + bs[3 * WS_H + j];
-    bv[1] = bs[WS_H + j] + bs[4 * WS_H + j];
-    bv[2] = bs[2 * WS_H + j];
-    bv[3] = bs[5 * WS_H + j];
-  }
+  cluster_bias(a.layer[layer].bias, WS_H, j, bv);
 
   // ---- zero the LDS state (h_{-1} = 0; X columns past I stay zero)
   {
@@ -241,60 +191,18 @@ __global__ void __launch_bounds__(256, 1) gru_ws_kernel(GruArgs a) {
     const int words = (2 * WS_M * WS_HS + 2 * WS_M * WS_XS) / 2;
     for (int i = tid; i < words; i += 256) z[i] = 0u;
   }
-  // ---- layer-1 input: chunk c = (row c / chunks, 8-element piece c % chunks); its source
-  // (event-ring slot / head / first valid step) goes to LDS once, and only the two layer-0
-  // waves stage x_{t+1} (<= 4 chunks per lane), so the layer-1 waves carry no staging registers
-  const int I = a.I;
-  const int chunks = I >> 3;  // 1..4
+  // ---- layer-1 input: the sources go to LDS once, and only the two layer-0 waves stage
+  // x_{t+1} (<= 4 chunks per lane), so the layer-1 waves carry no staging registers
+  const int chunks = a.I >> 3;  // 1..4
   const int nchunk = WS_M * chunks;
-  for (int c = tid; c < nchunk; c += 256) {
-    const int grow = row0 + c / chunks;
-    int slot = -1, head = 0, from = T;
-    if (grow < n_live) {
-      if (a.mode == 1) {
-        slot = a.slots[grow];
-        if (slot >= 0) {
-          const AcctRT r = a.rt[slot];
-          head = r.ev_head;
-          from = T - min(r.ev_count, T);
-        }
-      } else {
-        from = 0;
-      }
-    }
-    xmeta[c] = make_int2(slot, head | (from << 16));
-  }
-  auto load_x = [&](int c, int t) -> uint4 {
-    uint4 v = make_uint4(0, 0, 0, 0);
-    const int2 m = xmeta[c];
-    const int from = m.y >> 16;
-    if (t >= T) return v;
-    if (a.reverse) t = T - 1 - t;  // direction=reverse: forward over the time-reversed sequence
-    if (t < from) return v;
-    const int row = c / chunks, q = c - row * chunks;
-    if (a.mode == 1) {
-      if (m.x < 0) return v;
-      int idx = ((m.y & 0xffff) - T + t) % a.ev_ring;
-      if (idx < 0) idx += a.ev_ring;
-      v = *reinterpret_cast<const uint4*>(a.ev + (((size_t)m.x * a.ev_ring + idx) * I + q * 8));
-    } else {
-      const float* src = a.X + (((size_t)t * a.x_rows + row0 + row) * I + q * 8);
-      const float4 f0 = *reinterpret_cast<const float4*>(src);
-      const float4 f1 = *reinterpret_cast<const float4*>(src + 4);
-      v.x = (uint32_t)f32_to_bf16(f0.x) | ((uint32_t)f32_to_bf16(f0.y) << 16);
-      v.y = (uint32_t)f32_to_bf16(f0.z) | ((uint32_t)f32_to_bf16(f0.w) << 16);
-      v.z = (uint32_t)f32_to_bf16(f1.x) | ((uint32_t)f32_to_bf16(f1.y) << 16);
-      v.w = (uint32_t)f32_to_bf16(f1.z) | ((uint32_t)f32_to_bf16(f1.w) << 16);
-    }
-    return v;
-  };
+  cluster_x_sources<WS_M>(a, xmeta, row0, n_live, chunks, tid);
   auto x_slot = [&](int buf, int c) -> uint4* {
     const int row = c / chunks, q = c - row * chunks;
     return reinterpret_cast<uint4*>(Xb + buf * (WS_M * WS_XS) + row * WS_XS + q * 8);
   };
   __syncthreads();
   if (layer == 0)
-    for (int c = tid; c < nchunk; c += 128) *x_slot(0, c) = load_x(c, 0);
+    for (int c = tid; c < nchunk; c += 128) *x_slot(0, c) = cluster_load_x(a, xmeta, row0, chunks, c, 0);
 
   float hs[WS_RT][4];
 #pragma unroll
@@ -328,7 +236,7 @@ __global__ void __launch_bounds__(256, 1) gru_ws_kernel(GruArgs a) {
         const int row = (c >> 2) & (WS_M - 1), q = c & 3;
         const uint16_t* src = (i ? H2 : H1) + row * WS_HS + mem * WS_UW + q * 8;
         const u32x4 v = __builtin_bit_cast(u32x4, *reinterpret_cast<const uint4*>(src));
-        __builtin_amdgcn_raw_buffer_store_b128(v, xr, c * 16, ((par * WS_CL + mem) * WS_SLICE) * 2, SC1);
+        __builtin_amdgcn_raw_buffer_store_b128(v, xr, c * 16, ((par * WS_CL + mem) * WS_SLICE) * 2, kSC1);
       }
     };
     // the other seven members' slices of half h (14 chunks per thread) -> LDS
@@ -341,7 +249,7 @@ __global__ void __launch_bounds__(256, 1) gru_ws_kernel(GruArgs a) {
         m2 += m2 >= mem;
         const int w = k & 511;
         const int c = (w >> 8) * 512 + 256 * h + (w & 255);
-        v[i] = __builtin_amdgcn_raw_buffer_load_b128(xr, c * 16, ((par * WS_CL + m2) * WS_SLICE) * 2, SC1);
+        v[i] = __builtin_amdgcn_raw_buffer_load_b128(xr, c * 16, ((par * WS_CL + m2) * WS_SLICE) * 2, kSC1);
       }
 #pragma unroll
       for (int i = 0; i < 14; ++i) {
@@ -354,20 +262,6 @@ __global__ void __launch_bounds__(256, 1) gru_ws_kernel(GruArgs a) {
         *reinterpret_cast<uint4*>(((w >> 8) ? H2 : H1) + row * WS_HS + m2 * WS_UW + q * 8) = __builtin_bit_cast(uint4, v[i]);
       }
     };
-    // arrival (one lane) + bounded wait for all members; false: give up (the cluster exits)
-    auto arrive_wait = [&](int32_t* c, int target, bool arrive) -> bool {
-      if (tid == 0) {
-        if (arrive) __hip_atomic_fetch_add(c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        bool ok = true;
-        if (target > 0) {
-          ok = ws_wait(c, target, cnt);
-          if (!ok) atomicExch(a.ws_err, 1);
-        }
-        *sflag = ok;
-      }
-      __syncthreads();
-      return *sflag != 0;
-    };
     for (int t = 0; t <= T; ++t) {
       WS_MARK(t, 0);
       const bool act = layer == 0 ? (t < T) : (t >= 1);
@@ -377,7 +271,7 @@ __global__ void __launch_bounds__(256, 1) gru_ws_kernel(GruArgs a) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const int c = tid + 128 * u;
-          xn[u] = c < nchunk ? load_x(c, t + 1) : make_uint4(0, 0, 0, 0);
+          xn[u] = c < nchunk ? cluster_load_x(a, xmeta, row0, chunks, c, t + 1) : make_uint4(0, 0, 0, 0);
         }
         if (act) ws_layer<0, 0, WS_RT / 2>(wz, wr, wh, Xb + (t & 1) * (WS_M * WS_XS), H1, H2, hs, bv, lane);
 #pragma unroll
@@ -400,7 +294,7 @@ __global__ void __launch_bounds__(256, 1) gru_ws_kernel(GruArgs a) {
       __syncthreads();
       if (t < T) publish(0, t & 1);  // drains under the gather and half B's MFMAs
       if (t >= 1) {
-        if (!arrive_wait(cntB, WS_CL * t, false)) return;
+        if (!cluster_arrive_wait<true>(a, cntB, WS_CL * t, cnt, false, true, sflag, tid)) return;
         gather(1, (t - 1) & 1);
         __syncthreads();
       }
@@ -419,7 +313,7 @@ __global__ void __launch_bounds__(256, 1) gru_ws_kernel(GruArgs a) {
       __syncthreads();
       if (tid == 0) __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       publish(1, t & 1);
-      if (!arrive_wait(cnt, WS_CL * (t + 1), false)) return;
+      if (!cluster_arrive_wait<true>(a, cnt, WS_CL * (t + 1), cnt, false, true, sflag, tid)) return;
       gather(0, t & 1);
       __syncthreads();
       WS_MARK(t, 4);
@@ -433,7 +327,7 @@ __global__ void __launch_bounds__(256, 1) gru_ws_kernel(GruArgs a) {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int c = tid + 128 * u;
-        xn[u] = c < nchunk ? load_x(c, t + 1) : make_uint4(0, 0, 0, 0);
+        xn[u] = c < nchunk ? cluster_load_x(a, xmeta, row0, chunks, c, t + 1) : make_uint4(0, 0, 0, 0);
       }
       if (act) ws_layer<0>(wz, wr, wh, Xb + (t & 1) * (WS_M * WS_XS), H1, H2, hs, bv, lane);
 #pragma unroll
@@ -475,20 +369,14 @@ __global__ void __launch_bounds__(256, 1) gru_ws_kernel(GruArgs a) {
       const int L = c >> 9, row = (c >> 2) & (WS_M - 1), q = c & 3;
       const uint16_t* src = (L ? H2 : H1) + row * WS_HS + mem * WS_UW + q * 8;
       const u32x4 v = __builtin_bit_cast(u32x4, *reinterpret_cast<const uint4*>(src));
-      __builtin_amdgcn_raw_buffer_store_b128(v, xr, c * 16, ((par * WS_CL + mem) * WS_SLICE) * 2, SC1);
+      __builtin_amdgcn_raw_buffer_store_b128(v, xr, c * 16, ((par * WS_CL + mem) * WS_SLICE) * 2, kSC1);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     WS_MARK(t, 2);
-    if (tid == 0) {
-      __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const bool ok = ws_wait(cnt, WS_CL * (t + 1), cnt);
-      if (!ok) atomicExch(a.ws_err, 1);
-      *sflag = ok;
-    }
-    __syncthreads();
+    const bool ok = cluster_arrive_wait<true>(a, cnt, WS_CL * (t + 1), cnt, true, true, sflag, tid);
     WS_MARK(t, 3);
-    if (!*sflag) return;
+    if (!ok) return;
     // gather the other 7 members' slices into H1 / H2 (sc1 loads, 14 in flight per lane)
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -498,7 +386,7 @@ __global__ void __launch_bounds__(256, 1) gru_ws_kernel(GruArgs a) {
         const int c = (h * 14 + i) * 256 + tid;  // over 7 x 1024 chunks
         int m2 = c >> 10;
         m2 += m2 >= mem;
-        v[i] = __builtin_amdgcn_raw_buffer_load_b128(xr, (c & 1023) * 16, ((par * WS_CL + m2) * WS_SLICE) * 2, SC1);
+        v[i] = __builtin_amdgcn_raw_buffer_load_b128(xr, (c & 1023) * 16, ((par * WS_CL + m2) * WS_SLICE) * 2, kSC1);
       }
 #pragma unroll
       for (int i = 0; i < 14; ++i) {
@@ -516,64 +404,9 @@ __global__ void __launch_bounds__(256, 1) gru_ws_kernel(GruArgs a) {
 #undef WS_MARK
 
   // ---- outputs: layer-2 waves hold h2_{T-1} (f32) for rows 0..127 of their tile
-  if (layer == 1 && a.yh) {
-#pragma unroll
-    for (int rt = 0; rt < WS_RT; ++rt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = row0 + rt * 16 + crow + r;
-        if (row < n_live) a.yh[(size_t)row * WS_H + j] = hs[rt][r];
-      }
-  }
-  float* const part = a.ws_part + (size_t)cl * WS_CL * WS_M;
-  if (a.head_w) {
-    if (layer == 1) {
-      const float w = a.head_w[j];
-#pragma unroll
-      for (int rt = 0; rt < WS_RT; ++rt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float v = hs[rt][r] * w;
-#pragma unroll
-          for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
-          if (ccol == 0) red[(wave & 1) * WS_M + rt * 16 + crow + r] = v;
-        }
-    }
-    __syncthreads();
-    if (tid < WS_M) {
-      const float v = red[tid] + red[WS_M + tid];
-      __hip_atomic_store(part + mem * WS_M + tid, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  // final arrival: member 0 waits for all eight, combines the head partials, then returns the
-  // counter to 0 with an atomic (no member touches it again in this launch). The reset must
-  // take the atomic path: a memset node between graph replays left a stale counter line
-  // visible to the next replay's sc1 polls.
-  if (tid == 0) {
-    __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    bool ok = true;
-    if (mem == 0) {
-      ok = ws_wait(cnt, WS_CL * (T + 1), cnt);
-      if (!ok) atomicExch(a.ws_err, 1);
-    }
-    *sflag = ok;
-  }
-  __syncthreads();
-  if (mem != 0 || !*sflag) return;
-  if (a.head_w && tid < WS_M && row0 + tid < n_live) {
-    float v = a.head_b;
-#pragma unroll
-    for (int m2 = 0; m2 < WS_CL; ++m2)
-      v += __hip_atomic_load(part + m2 * WS_M + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (a.head_act == 2) v = 1.f / (1.f + expf(-v));
-    a.out[row0 + tid] = v;
-  }
-  if (tid == 0) {
-    __hip_atomic_exchange(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (SPLIT) __hip_atomic_exchange(cnt + 8, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  if (layer == 1) cluster_emit<WS_RT>(a, hs, row0, n_live, j, crow, ccol, red + (wave & 1) * WS_M);
+  if (a.head_w) __syncthreads();
+  cluster_finish<WS_CL, WS_M, 2, true, SPLIT>(a, cnt, cl, mem, row0, n_live, red, sflag, tid);
 }
 
 // ============================================================================================
@@ -643,19 +476,9 @@ __device__ __forceinline__ void w2_layer(const bf16x8 (&wz)[16], const bf16x8 (&
     f32x4 acc[4];
     w2_tile<L>(wz, wr, wh, X, H1, H2, rt, lane, acc);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float z = sig_(acc[0][r] + bv[0]);
-      const float rr = sig_(acc[1][r] + bv[1]);
-      const float hh = tanh_(acc[2][r] + bv[2] + rr * (acc[3][r] + bv[3]));
-      hs[rt][r] = (1.f - z) * hh + z * hs[rt][r];
-    }
+    for (int r = 0; r < 4; ++r) hs[rt][r] = cluster_gate(acc[0][r], acc[1][r], acc[2][r], acc[3][r], bv, hs[rt][r]);
   }
 }
-
-template <int L>
-struct W2Layer {
-  static constexpr int value = L;
-};
 
 __global__ void __launch_bounds__(256, 2) gru_ws2_kernel(GruArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -695,37 +518,17 @@ __global__ void __launch_bounds__(256, 2) gru_ws2_kernel(GruArgs a) {
   const int j = ht * 16 + ccol;
   const int T = a.T;
   int32_t* const cnt = a.ws_sync + cl * 16;
-  if (a.head_w && mem == 0 && tid < W2_M && row0 + tid < n_live) a.out[row0 + tid] = __builtin_nanf("");
-  if (a.yh)
-    for (int e = tid; e < W2_M * WS_UW; e += 256) {
-      const int row = row0 + e / WS_UW;
-      if (row < n_live) a.yh[(size_t)row * WS_H + mem * WS_UW + e % WS_UW] = __builtin_nanf("");
-    }
+  cluster_nan_fill<W2_M, WS_UW>(a, row0, n_live, mem, tid);
   {
     uint32_t* z = reinterpret_cast<uint32_t*>(smem);
     const int words = (2 * WS_CL * W2_BLK + 2 * W2_M * WS_XS) / 2;
     for (int i = tid; i < words; i += 256) z[i] = 0u;
   }
-  const int I = a.I;
-  const int chunks = I >> 3;
+  const int chunks = a.I >> 3;
   const int nchunk = W2_M * chunks;  // <= 256
-  for (int c = tid; c < nchunk; c += 256) {
-    const int grow = row0 + c / chunks;
-    int slot = -1, head = 0, from = T;
-    if (grow < n_live) {
-      if (a.mode == 1) {
-        slot = a.slots[grow];
-        if (slot >= 0) {
-          const AcctRT r = a.rt[slot];
-          head = r.ev_head;
-          from = T - min(r.ev_count, T);
-        }
-      } else {
-        from = 0;
-      }
-    }
-    xmeta[c] = make_int2(slot, head | (from << 16));
-  }
+  cluster_x_sources<W2_M>(a, xmeta, row0, n_live, chunks, tid);
+  // This kernel keeps its own copy of gru_cluster.h's cluster_load_x (and of cluster_emit, below):
+  // through the shared helpers the same statements cost it 4 to 20 B more scratch at 256 VGPRs.
   auto load_x = [&](int c, int t) -> uint4 {
     uint4 v = make_uint4(0, 0, 0, 0);
     const int2 m = xmeta[c];
@@ -734,21 +537,16 @@ __global__ void __launch_bounds__(256, 2) gru_ws2_kernel(GruArgs a) {
     if (a.reverse) t = T - 1 - t;
     if (t < from) return v;
     const int row = c / chunks, q = c - row * chunks;
+    SeqSrc s = {m.x, m.y & 0xffff, from};
     if (a.mode == 1) {
       if (m.x < 0) return v;
-      int idx = ((m.y & 0xffff) - T + t) % a.ev_ring;
-      if (idx < 0) idx += a.ev_ring;
-      v = *reinterpret_cast<const uint4*>(a.ev + (((size_t)m.x * a.ev_ring + idx) * I + q * 8));
-    } else {
-      const float* src = a.X + (((size_t)t * a.x_rows + row0 + row) * I + q * 8);
-      const float4 f0 = *reinterpret_cast<const float4*>(src);
-      const float4 f1 = *reinterpret_cast<const float4*>(src + 4);
-      v.x = (uint32_t)f32_to_bf16(f0.x) | ((uint32_t)f32_to_bf16(f0.y) << 16);
-      v.y = (uint32_t)f32_to_bf16(f0.z) | ((uint32_t)f32_to_bf16(f0.w) << 16);
-      v.z = (uint32_t)f32_to_bf16(f1.x) | ((uint32_t)f32_to_bf16(f1.y) << 16);
-      v.w = (uint32_t)f32_to_bf16(f1.z) | ((uint32_t)f32_to_bf16(f1.w) << 16);
+      return seq_ring_chunk(a, s, q, t);
     }
-    return v;
+    float f[8];
+    uint16_t h[8];
+    seq_dense_chunk(a, row0 + row, q, t, f);
+    for (int e = 0; e < 8; ++e) h[e] = f32_to_bf16(f[e]);
+    return bf16_pack8(h);
   };
   auto x_slot = [&](int buf, int c) -> uint4* {
     const int row = c / chunks, q = c - row * chunks;
@@ -773,39 +571,9 @@ __global__ void __launch_bounds__(256, 2) gru_ws2_kernel(GruArgs a) {
   auto run = [&](auto Lc) -> bool {
     constexpr int L = decltype(Lc)::value;
     bf16x8 wz[16], wr[16], wh[16];
-    if constexpr (L == 0) {
-      const uint16_t* W = a.layer[0].W;
-      const uint16_t* R = a.layer[0].R;
-      wz[0] = wfrag(W, ht, 1, 0, lane);
-      wr[0] = wfrag(W, WS_HT + ht, 1, 0, lane);
-      wh[0] = wfrag(W, 2 * WS_HT + ht, 1, 0, lane);
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks) {
-        wz[1 + ks] = wfrag(R, ht, 8, ks, lane);
-        wr[1 + ks] = wfrag(R, WS_HT + ht, 8, ks, lane);
-        wh[1 + ks] = wfrag(R, 2 * WS_HT + ht, 8, ks, lane);
-      }
-    } else {
-      const uint16_t* W = a.layer[1].W;
-      const uint16_t* R = a.layer[1].R;
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks) {
-        wz[ks] = wfrag(W, ht, 8, ks, lane);
-        wr[ks] = wfrag(W, WS_HT + ht, 8, ks, lane);
-        wh[ks] = wfrag(W, 2 * WS_HT + ht, 8, ks, lane);
-        wz[8 + ks] = wfrag(R, ht, 8, ks, lane);
-        wr[8 + ks] = wfrag(R, WS_HT + ht, 8, ks, lane);
-        wh[8 + ks] = wfrag(R, 2 * WS_HT + ht, 8, ks, lane);
-      }
-    }
+    ws_load_weights<L>(a, ht, lane, wz, wr, wh);
     float bv[4];
-    {
-      const float* bs = a.layer[L].bias;
-      bv[0] = bs[j] + bs[3 * WS_H + j];
-      bv[1] = bs[WS_H + j] + bs[4 * WS_H + j];
-      bv[2] = bs[2 * WS_H + j];
-      bv[3] = bs[5 * WS_H + j];
-    }
+    cluster_bias(a.layer[L].bias, WS_H, j, bv);
     float hs[W2_RT][4];
 #pragma unroll
     for (int rt = 0; rt < W2_RT; ++rt)
@@ -855,20 +623,14 @@ __global__ void __launch_bounds__(256, 2) gru_ws2_kernel(GruArgs a) {
         const int c = i * 256 + tid;
         const uint16_t* src = ((c >> 8) ? H2 : H1) + mem * W2_BLK + (c & 255) * 8;
         const u32x4 v = __builtin_bit_cast(u32x4, *reinterpret_cast<const uint4*>(src));
-        __builtin_amdgcn_raw_buffer_store_b128(v, xr, c * 16, ((par * WS_CL + mem) * W2_SLICE) * 2, SC1);
+        __builtin_amdgcn_raw_buffer_store_b128(v, xr, c * 16, ((par * WS_CL + mem) * W2_SLICE) * 2, kSC1);
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       WS_MARK(t, 2);
-      if (tid == 0) {
-        __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const bool ok = ws_wait(cnt, WS_CL * (t + 1), cnt);
-        if (!ok) atomicExch(a.ws_err, 1);
-        *sflag = ok;
-      }
-      __syncthreads();
+      const bool ok = cluster_arrive_wait<true>(a, cnt, WS_CL * (t + 1), cnt, true, true, sflag, tid);
       WS_MARK(t, 3);
-      if (!*sflag) return false;
+      if (!ok) return false;
       // the other 7 members' slices straight into the LDS image: 7 x 8 KB = 56 global_load_lds
       // of 1 KB (14 per wave), sc1 (L2-coherent); the barrier below waits vmcnt(0) for them
       {
@@ -882,7 +644,7 @@ __global__ void __launch_bounds__(256, 2) gru_ws2_kernel(GruArgs a) {
           const uint16_t* src = slab + (size_t)m2 * W2_SLICE + Lg * W2_BLK + kb * 512 + lane * 8;
           uint16_t* dst = (Lg ? H2 : H1) + m2 * W2_BLK + kb * 512;
           __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)(src),
-                                           (__attribute__((address_space(3))) void*)(dst), 16, 0, SC1);
+                                           (__attribute__((address_space(3))) void*)(dst), 16, 0, kSC1);
         }
       }
       __syncthreads();
@@ -914,39 +676,11 @@ __global__ void __launch_bounds__(256, 2) gru_ws2_kernel(GruArgs a) {
     }
     return true;
   };
-  const bool ok_run = layer == 0 ? run(W2Layer<0>{}) : run(W2Layer<1>{});
+  const bool ok_run = layer == 0 ? run(std::integral_constant<int, 0>{}) : run(std::integral_constant<int, 1>{});
   if (!ok_run) return;
 
-  float* const part = a.ws_part + (size_t)cl * WS_CL * W2_M;
-  if (a.head_w) {
-    __syncthreads();
-    if (tid < W2_M) {
-      const float v = red[tid] + red[W2_M + tid];
-      __hip_atomic_store(part + mem * W2_M + tid, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    bool ok = true;
-    if (mem == 0) {
-      ok = ws_wait(cnt, WS_CL * (T + 1), cnt);
-      if (!ok) atomicExch(a.ws_err, 1);
-    }
-    *sflag = ok;
-  }
-  __syncthreads();
-  if (mem != 0 || !*sflag) return;
-  if (a.head_w && tid < W2_M && row0 + tid < n_live) {
-    float v = a.head_b;
-#pragma unroll
-    for (int m2 = 0; m2 < WS_CL; ++m2)
-      v += __hip_atomic_load(part + m2 * W2_M + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (a.head_act == 2) v = 1.f / (1.f + expf(-v));
-    a.out[row0 + tid] = v;
-  }
-  if (tid == 0) __hip_atomic_exchange(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (a.head_w) __syncthreads();
+  cluster_finish<WS_CL, W2_M, 2, true, false>(a, cnt, cl, mem, row0, n_live, red, sflag, tid);
 }
 
 }  // namespace

@@ -289,7 +289,6 @@ void launch_ensemble(const EnsembleArgs& a, hipStream_t st);
 // zeroes them when it falls back (GruPack.disable_ws) - a successful launch leaves them at 0.
 constexpr int32_t kClusterPoison = -(1 << 30);
 
-// ---- K4 GRU sequence (recurrent weights resident in VGPRs)
 // ---- K4 GRU (1-2 stacked ONNX GRU layers, forward, layout 0) + optional N=1 head
 // Weights are fragment-packed on the host: P[nt][ks][lane][8] = W[nt*16 + (lane&15)]
 // [ks*32 + 8*(lane>>4) + j], so one wave load of a B fragment is 1 KiB contiguous.
@@ -326,12 +325,15 @@ struct GruArgs {
   // weight-stationary cluster path (gru_ws.hip), used when the workspace is given and the
   // model is the 2 x 256, linear_before_reset = 1, input <= 32 shape
   int32_t ws;               // 0 off | 1 use when eligible | 2 two-half pipeline | 3 two 64-row clusters per CU
-  int32_t ws_clusters;      // workspace capacity in 128-row clusters
+  // the workspace is sized in the kernel's clusters: 128 rows (ws = 1, 2), 64 rows (ws = 3: two per
+  // 128-row cluster of capacity) or 32 rows (split mode, gru_wsx.hip, below)
+  int32_t ws_clusters;      // workspace capacity in 128-row clusters (split mode: 32-row clusters)
   int32_t* ws_sync;         // [2 ws_clusters][16] step counters (back to 0 after every launch)
-  uint16_t* ws_x;           // [ws_clusters][2][8][2][128][32] bf16 hand-off slabs
-  float* ws_part;           // [ws_clusters][8][128] head partials
+  uint16_t* ws_x;           // [ws_clusters][2][8][2][128][32] bf16 hand-off slabs (ws = 3: [2 ws_clusters][2][8][2][64][32])
+  float* ws_part;           // [ws_clusters][8][128] head partials (ws = 3: [2 ws_clusters][8][64])
   int32_t* ws_err;          // [1] set when a cluster was not co-resident (bounded wait expired)
-  int64_t* ws_trace;        // [64][6] phase timestamps of workgroup 0 (nullable; tools/gru_bench.py)
+  int64_t* ws_trace;        // 64 * 8 + 4 + 1024 words (nullable): per-step phase timestamps of workgroup 0, clocks,
+                            // workgroup placement (tools/gru_ws_trace.py, tools/gru_wsx_trace.py)
   int32_t split;            // 1: f32-faithful bf16 hi/lo pairs, three MFMAs per product (gru.hip x3)
   int32_t reverse;          // 1: ONNX direction=reverse (every layer): time steps read last to first
   // ONNX sequence_lens: a row is updated on its live steps only and holds h on every other one.

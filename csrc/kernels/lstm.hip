@@ -15,8 +15,10 @@
 // SPLIT = 1 (fp32 plans): weights and activations are bf16 pairs hi + lo, each product three
 // MFMAs (lo*hi + hi*lo + hi*hi) into f32 accumulators, activation tiles doubled in LDS.
 // SPLIT = 0 (bf16 plans): one MFMA per product.
+// The layer-1 input staging is seq_input.h's, shared with gru.hip and the cluster kernels.
 #include "common.h"
 #include "launch.h"
+#include "seq_input.h"
 #include "seq_window.h"
 
 namespace igp {
@@ -55,16 +57,6 @@ __device__ __forceinline__ bf16x8 ld_frag(const WFrag& w, int nt, int KS, int ks
 __device__ __forceinline__ bf16x8 lds_frag(const uint16_t* base, int stride, int row, int k) {
   const uint4 v = *reinterpret_cast<const uint4*>(base + row * stride + k);
   return *reinterpret_cast<const bf16x8*>(&v);
-}
-
-__device__ __forceinline__ void split_bf16(float x, uint16_t& hi, uint16_t& lo) {
-  hi = f32_to_bf16(x);
-  lo = f32_to_bf16(x - __uint_as_float((uint32_t)hi << 16));
-}
-
-__device__ __forceinline__ uint4 pack8(const uint16_t (&v)[8]) {
-  return make_uint4(v[0] | (uint32_t)v[1] << 16, v[2] | (uint32_t)v[3] << 16, v[4] | (uint32_t)v[5] << 16,
-                    v[6] | (uint32_t)v[7] << 16);
 }
 
 // acc += a . b: one MFMA, or the three of the hi / lo split (lo*lo ~2^-18 relative is dropped)
@@ -152,7 +144,7 @@ __device__ __forceinline__ void lstm_step(const WPair& gW, const WPair& gR, cons
         cs[i][rt][r] = c;
         hs[i][rt][r] = h;
         const int o = (rt * 16 + crow + r) * HS + j;
-        if constexpr (SPLIT != 0) split_bf16(h, hnext[o], hnextl[o]);
+        if constexpr (SPLIT != 0) bf16_split(h, hnext[o], hnextl[o]);
         else hnext[o] = f32_to_bf16(h);
       }
   }
@@ -264,52 +256,22 @@ __global__ void __launch_bounds__(NW * 64) lstm_kernel(LstmArgs a) {
   }
 
   // ---- layer-1 input staging: thread -> (row rr, 8-element chunk c), fixed for all t
-  const int I = a.I;
-  const int chunks = I >> 3;
+  const int chunks = a.I >> 3;
   const int my_rr = tid / max(chunks, 1), my_c = tid - my_rr * max(chunks, 1);
   const bool stager = chunks > 0 && my_rr < M;
   const int grow = row0 + my_rr;
-  int slot = -1, head = 0, valid_from = a.T;
-  if (stager && grow < n_live) {
-    if (a.mode == 1) {
-      slot = a.slots[grow];
-      if (slot >= 0) {
-        const AcctRT r = a.rt[slot];
-        head = r.ev_head;
-        valid_from = a.T - min(r.ev_count, a.T);
-      }
-    } else {
-      valid_from = 0;
-    }
-  }
-  // x_t as (hi, lo) bf16 halves: the event ring holds bf16 values (lo = 0); dense f32 input splits
+  const SeqSrc src = stager ? seq_src(a, grow, n_live) : SeqSrc{-1, 0, a.T};
+  // x_t as (hi, lo) bf16 halves; a bf16 (SPLIT = 0) kernel never stores lo
   auto load_x = [&](int t, uint4& hi, uint4& lo) {
-    hi = lo = make_uint4(0, 0, 0, 0);
-    if (t >= a.T) return;
-    if (a.reverse) t = a.T - 1 - t;  // direction=reverse: forward over the time-reversed sequence
-    if (!stager || t < valid_from) return;
-    if (a.mode == 1) {
-      int idx = (head - a.T + t) % a.ev_ring;
-      if (idx < 0) idx += a.ev_ring;
-      hi = *reinterpret_cast<const uint4*>(a.ev + (((size_t)slot * a.ev_ring + idx) * I + my_c * 8));
-    } else {
-      const float* src = a.X + (((size_t)t * a.x_rows + grow) * I + my_c * 8);
-      const float4 f0 = *reinterpret_cast<const float4*>(src);
-      const float4 f1 = *reinterpret_cast<const float4*>(src + 4);
-      const float f[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
-      uint16_t h8[8], l8[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) split_bf16(f[e], h8[e], l8[e]);
-      hi = pack8(h8);
-      if constexpr (SPLIT != 0) lo = pack8(l8);
-    }
+    if constexpr (SPLIT != 0) seq_load_split(a, src, grow, my_c, t, hi, lo);
+    else hi = seq_load(a, src, grow, my_c, t);
   };
   auto store_x = [&](int b, const uint4& hi, const uint4& lo) {
     *reinterpret_cast<uint4*>(XB(0, b) + my_rr * XS + my_c * 8) = hi;
     if constexpr (SPLIT != 0) *reinterpret_cast<uint4*>(XB(1, b) + my_rr * XS + my_c * 8) = lo;
   };
   if constexpr (MASKED != 0) {
-    if (stager && my_c == 0) reinterpret_cast<uint32_t*>(red + NW * M)[my_rr] = seq_window(a, grow, n_live, valid_from);
+    if (stager && my_c == 0) reinterpret_cast<uint32_t*>(red + NW * M)[my_rr] = seq_window(a, grow, n_live, src.from);
   }
   __syncthreads();  // zeroing done before the first staged row lands
   if (stager) {
