@@ -344,6 +344,59 @@ PYBIND11_MODULE(_hipk, m) {
     const GemmArgs a = gemm_args(d);
     launch_or_record([a](hipStream_t st) { launch_gemv(a, st); }, s, "gemv");
   });
+  m.attr("Q_MAX_K") = Q_MAX_K;
+  m.def("qgemm_tile", [](int M, int N) { return qgemm_tile(M, N); });
+  m.def("qgemm", [](py::dict d, uintptr_t s) {
+    QGemmArgs a{};
+    a.X = ptr<const int8_t*>(d, "X");
+    a.W = ptr<const int8_t*>(d, "W");
+    a.corr = ptr<const int32_t*>(d, "corr");
+    a.mult = ptr<const float*>(d, "mult");
+    a.bias = ptr<const float*>(d, "bias");
+    a.Y = ptr<void*>(d, "Y");
+    a.m_ptr = ptr<const int32_t*>(d, "m_ptr");
+    a.M = geti(d, "M");
+    a.N = geti(d, "N");
+    a.K = geti(d, "K");
+    a.ldx = geti(d, "ldx");
+    a.ldy = geti(d, "ldy");
+    a.ldw = geti(d, "ldw");
+    a.y_kind = geti(d, "y_kind");
+    a.act = geti(d, "act");
+    a.y_scale = d.contains("y_scale") ? d["y_scale"].cast<float>() : 1.f;
+    a.y_zp = geti(d, "y_zp");
+    a.y_off = geti(d, "y_off");
+    const int w_rows = geti(d, "w_rows");
+    if (!a.X || !a.W || !a.corr || !a.mult || !a.Y) throw std::runtime_error("qgemm: missing pointers");
+    if (a.M < 0 || a.N < 1 || a.K < 1 || a.K > Q_MAX_K || a.ldx < a.K || a.ldy < a.N)
+      throw std::runtime_error("qgemm: sizes (1 <= K <= 32768, ldx >= K, ldy >= N)");
+    if (a.ldw % 64 || a.ldw < a.K || w_rows % 128 || w_rows < a.N)
+      throw std::runtime_error("qgemm: W must be padded to [N_pad % 128 == 0][K_pad % 64 == 0]");
+    if (a.y_kind < QY_F32 || a.y_kind > QY_Q8 || a.act < 0 || a.act > 3) throw std::runtime_error("qgemm: y_kind / act");
+    if (a.y_kind == QY_Q8 && (!(a.y_scale > 0.f) || (a.y_off != 0 && a.y_off != 128) || a.y_zp < a.y_off - 128 ||
+                              a.y_zp > a.y_off + 127))
+      throw std::runtime_error("qgemm: output quantisation (scale > 0, off 0 | 128, zero point inside the type)");
+    launch_or_record([a](hipStream_t st) { launch_qgemm(a, st); }, s, "qgemm");
+  });
+  m.def("quant_rows", [](py::dict d, uintptr_t s) {
+    QuantRowsArgs a{};
+    a.F = ptr<void*>(d, "F");
+    a.Q = ptr<int8_t*>(d, "Q");
+    a.m_ptr = ptr<const int32_t*>(d, "m_ptr");
+    a.M = geti(d, "M");
+    a.N = geti(d, "N");
+    a.ldf = geti(d, "ldf");
+    a.ldq = geti(d, "ldq");
+    a.f_bf16 = geti(d, "f_bf16");
+    a.dequant = geti(d, "dequant");
+    a.scale = d["scale"].cast<float>();
+    a.zp = geti(d, "zp");
+    a.off = geti(d, "off");
+    if (!a.F || !a.Q || a.N < 1 || a.M < 0 || a.ldf < a.N || a.ldq < a.N) throw std::runtime_error("quant_rows: args");
+    if (!(a.scale > 0.f) || (a.off != 0 && a.off != 128) || a.zp < a.off - 128 || a.zp > a.off + 127)
+      throw std::runtime_error("quant_rows: scale > 0, off 0 | 128, zero point inside the type");
+    launch_or_record([a](hipStream_t st) { launch_quant_rows(a, st); }, s, "quant_rows");
+  });
   m.def("join", [](py::dict d, uintptr_t s) {
     JoinArgs a{};
     a.A = ptr<const void*>(d, "A");

@@ -209,6 +209,43 @@ struct GemmArgs {
 void launch_gemm(const GemmArgs& a, hipStream_t st);
 void launch_gemv(const GemmArgs& a, hipStream_t st);  // N == 1 heads
 
+// ---- K3 quantised dense layers (qgemm.hip): int8 x int8 -> int32 on v_mfma_i32_16x16x64_i8,
+// Y = act(float(acc + corr[n]) * mult[n] + bias[n]), optionally requantised. A quantised value q
+// (uint8 / int8) is stored as the signed byte q - off, off = 128 / 0.
+enum QOut : int32_t { QY_F32 = 0, QY_BF16 = 1, QY_Q8 = 2 };
+constexpr int Q_MAX_K = 32768;  // acc + corr stays inside int32 up to here
+struct QGemmArgs {
+  const int8_t* X;          // [M][ldx] stored bytes q_x - off_x
+  const int8_t* W;          // [N_pad(128)][ldw = K_pad(64)] w_q - z_w, zero padded
+  const int32_t* corr;      // [N] (off_x - z_x) * sum_k W[n][k]
+  const float* mult;        // [N] s_x * s_w[n] * alpha
+  const float* bias;        // [N] nullable
+  void* Y;                  // [M][ldy] f32 / bf16 / stored bytes (y_kind)
+  const int32_t* m_ptr;     // live rows in device memory (nullable -> M)
+  int32_t M, N, K;
+  int32_t ldx, ldy, ldw;
+  int32_t y_kind;           // QOut
+  int32_t act;              // 0 none, 1 relu, 2 sigmoid, 3 tanh
+  float y_scale;            // QY_Q8: Y = clamp(rintf(v / y_scale) + y_zp) - y_off
+  int32_t y_zp, y_off;
+};
+void launch_qgemm(const QGemmArgs& a, hipStream_t st);
+int qgemm_tile(int M, int N);  // rows = columns of the output tile launch_qgemm picks (64 | 128)
+
+// QuantizeLinear (F -> Q) / DequantizeLinear (Q -> F) of one [M][N] tensor, per-tensor parameters
+struct QuantRowsArgs {
+  void* F;                  // [M][ldf] f32 or bf16: read (quantise) or written (dequant)
+  int8_t* Q;                // [M][ldq] stored bytes q - off: written (quantise) or read
+  const int32_t* m_ptr;     // live rows in device memory (nullable -> M)
+  int32_t M, N;
+  int32_t ldf, ldq;
+  int32_t f_bf16;
+  int32_t dequant;          // 0: Q = clamp(rintf(F / scale) + zp) - off; 1: F = (Q + off - zp) * scale
+  float scale;
+  int32_t zp, off;
+};
+void launch_quant_rows(const QuantRowsArgs& a, hipStream_t st);
+
 // DAG join of two branches (join.hip): op 0 Y = A + B (na columns), op 1 Y = [A | B]
 struct JoinArgs {
   const void* A;

@@ -178,6 +178,12 @@ PYBIND11_MODULE(_native, m) {
         if (it == mm.graph.initializers.end()) throw py::key_error(name);
         return tensor_to_np(it->second);
       })
+      // ONNX element type of an initializer as the file stores it (uint8 / int8 / int32 arrive widened to int64)
+      .def("initializer_dtype", [](const onnx::Model& mm, const std::string& name) {
+        auto it = mm.graph.initializers.find(name);
+        if (it == mm.graph.initializers.end()) throw py::key_error(name);
+        return it->second.elem;
+      })
       .def("nodes", [](const onnx::Model& mm) {
         py::list l;
         for (auto& n : mm.graph.nodes) {

@@ -82,6 +82,73 @@ Tensor unary(const Tensor& A, const std::function<float(float)>& op) {
 
 inline float sigmoid(float x) { return 1.f / (1.f + std::exp(-x)); }
 
+// ---- ai.onnx QDQ quantisation (opset 10 / 13 forms). Tensors stay float: a quantised value is an
+// integer of at most 9 bits held in a float, tagged with its type in Tensor::elem.
+const char* const kQdqOnly = " is not supported: quantised models run in the QDQ format (QuantizeLinear / "
+                             "DequantizeLinear around float Gemm / MatMul)";
+
+void qdq_attrs(const onnx::Node& n) {
+  if (n.geti("block_size", 0) != 0) throw std::runtime_error(n.op_type + ": block_size (blocked quantisation) is not supported");
+  if (n.geti("saturate", 1) != 1) throw std::runtime_error(n.op_type + ": saturate=0 is not supported");
+  if (const auto* a = n.attr("output_dtype"))
+    if (a->i != 0 && a->i != onnx::UINT8 && a->i != onnx::INT8)
+      throw std::runtime_error(n.op_type + ": output_dtype " + std::to_string(a->i) + " is not supported (uint8 and int8 only)");
+}
+
+// the quantised type a zero point gives (absent: uint8); its range in lo / hi
+int32_t quant_type(const std::string& op, const Tensor* zp, int32_t dflt, float& lo, float& hi) {
+  const int32_t t = zp ? zp->elem : dflt;
+  if (t == onnx::UINT8) { lo = 0.f; hi = 255.f; }
+  else if (t == onnx::INT8) { lo = -128.f; hi = 127.f; }
+  else throw std::runtime_error(op + ": zero point of ONNX type " + std::to_string(t) + " is not supported (uint8 and int8 only)");
+  return t;
+}
+
+Tensor quantize_linear(const onnx::Node& n, const Tensor& x, const Tensor& scale, const Tensor* zp) {
+  qdq_attrs(n);
+  if (x.dtype != FLOAT) throw std::runtime_error("QuantizeLinear: the input must be a float tensor");
+  if (scale.dtype != FLOAT || scale.numel() != 1 || (zp && zp->numel() != 1))
+    throw std::runtime_error("QuantizeLinear: per-axis quantisation of activations is not supported (one scale, one zero point)");
+  float lo, hi;
+  const int32_t a_out = int32_t(n.geti("output_dtype", 0));
+  const int32_t t = quant_type("QuantizeLinear", zp, a_out ? a_out : int32_t(onnx::UINT8), lo, hi);
+  const float s = scale.f[0], z = zp ? float(zp->i[0]) : 0.f;
+  Tensor y = make(x.dims);
+  y.elem = t;
+  // saturate(round_half_even(x / s) + z): a true float division, rint in the default rounding mode
+  for (size_t k = 0; k < x.f.size(); ++k) y.f[k] = std::min(hi, std::max(lo, std::rint(x.f[k] / s) + z));
+  return y;
+}
+
+Tensor dequantize_linear(const onnx::Node& n, const Tensor& x, const Tensor& scale, const Tensor* zp) {
+  qdq_attrs(n);
+  if (scale.dtype != FLOAT) throw std::runtime_error("DequantizeLinear: the scale must be a float tensor");
+  const bool is_int = x.dtype != FLOAT;  // an initializer: uint8 / int8 weights, int32 bias
+  if (is_int && x.elem != onnx::UINT8 && x.elem != onnx::INT8 && x.elem != onnx::INT32)
+    throw std::runtime_error("DequantizeLinear: input of ONNX type " + std::to_string(x.elem) + " is not supported (uint8, int8, int32)");
+  if (zp && zp->dtype == FLOAT) throw std::runtime_error("DequantizeLinear: the zero point must be an integer tensor");
+  if (zp && zp->numel() != scale.numel()) throw std::runtime_error("DequantizeLinear: scale and zero point differ in size");
+  const int64_t ns = scale.numel();
+  int64_t len = 1, inner = 1;
+  if (ns != 1) {  // per-axis: weights and biases only
+    if (!is_int) throw std::runtime_error("DequantizeLinear: per-axis quantisation of activations is not supported");
+    const int64_t ax = norm_axis(n.geti("axis", 1), x.dims.size());
+    if (ax >= int64_t(x.dims.size()) || x.dims[ax] != ns)
+      throw std::runtime_error("DequantizeLinear: the scale length differs from the axis dimension");
+    len = ns;
+    for (size_t d = ax + 1; d < x.dims.size(); ++d) inner *= x.dims[d];
+  }
+  Tensor y = make(x.dims);
+  const int64_t total = x.numel();
+  for (int64_t e = 0; e < total; ++e) {
+    const int64_t c = len == 1 ? 0 : (e / inner) % len;
+    const double q = is_int ? double(x.i[e]) : double(x.f[e]);
+    const double z = zp ? double(zp->i[c]) : 0.0;
+    y.f[e] = float((q - z) * double(scale.f[c]));  // exact integer difference, one rounding
+  }
+  return y;
+}
+
 Tensor gemm(const onnx::Node& n, const Tensor& A, const Tensor& B, const Tensor* C) {
   const float alpha = n.getf("alpha", 1.f), beta = n.getf("beta", 1.f);
   const bool ta = n.geti("transA", 0), tb = n.geti("transB", 0);
@@ -767,6 +834,16 @@ std::map<std::string, Tensor> Executor::run(const std::map<std::string, Tensor>&
       const Tensor& x = get(n.inputs[0]);
       out = make(x.dims);
       out.f = as_float(x);
+    } else if (op == "QuantizeLinear" || op == "DequantizeLinear") {
+      if (n.inputs.size() < 2) throw std::runtime_error(op + ": needs a value and a scale");
+      for (size_t i = 1; i < n.inputs.size() && i < 3; ++i)
+        if (!n.inputs[i].empty() && !g.initializers.count(n.inputs[i]))
+          throw std::runtime_error(op + ": scale and zero point must be constants (initializers)");
+      out = op == "QuantizeLinear" ? quantize_linear(n, get(n.inputs[0]), get(n.inputs[1]), opt(n, 2))
+                                   : dequantize_linear(n, get(n.inputs[0]), get(n.inputs[1]), opt(n, 2));
+    } else if (op == "QLinearMatMul" || op == "QLinearConv" || op == "QLinearAdd" || op == "QGemm" ||
+               op == "MatMulInteger" || op == "ConvInteger" || op == "DynamicQuantizeLinear") {
+      throw std::runtime_error("executor: " + op + kQdqOnly);
     } else if (op == "GRU") {
       Tensor Y, Yh;
       gru(n, get(n.inputs[0]), get(n.inputs[1]), get(n.inputs[2]), opt(n, 3), opt(n, 4),

@@ -19,6 +19,9 @@ enum DType : int32_t { FLOAT = 1, UINT8 = 2, INT8 = 3, INT32 = 6, INT64 = 7, STR
 struct Tensor {
   std::string name;
   int32_t dtype = FLOAT;
+  // element type as the file stores it: UINT8 / INT8 / INT32 / BOOL initializers are widened to
+  // int64 payloads (dtype INT64) and keep their type here; QuantizeLinear tags its output with it
+  int32_t elem = 0;
   std::vector<int64_t> dims;
   std::vector<float> f;
   std::vector<int64_t> i;

@@ -31,6 +31,7 @@ void parse_tensor(std::string_view buf, Tensor& t) {
     }
   }
   const int64_t n = t.numel();
+  t.elem = t.dtype;
   auto need = [&](size_t bytes) {
     if (raw.size() != bytes)
       throw std::runtime_error("onnx: raw_data size mismatch for tensor " + t.name);

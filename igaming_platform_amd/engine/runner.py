@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from ..models.plan import Plan, has_sequence, step_consumers, step_inputs
+from ..models.plan import Plan, has_sequence, step_consumers, step_inputs, step_qtype
 from ..ops import kernels as K
 
 
@@ -140,13 +140,18 @@ class DeviceModel:
         for i, s in enumerate(steps):
             last = i == len(steps) - 1
             cons = self.consumers[i]
-            feeds_mma = (not last) and bool(cons) and all(steps[j].kind in ("dense", "head", "join", "row") for j in cons)
-            # bf16 plans hand bf16 activations to the MFMA layers reading them (joins and row steps
-            # pass them on in the same dtype); fp32 plans stay f32
-            dt = (torch.bfloat16 if (s.kind in ("dense", "gru", "lstm", "join", "row") and feeds_mma
-                                     and plan.precision == "bf16")
+            feeds_mma = (not last) and bool(cons) and all(steps[j].kind in ("dense", "head", "join", "row", "quant")
+                                                          for j in cons)
+            # bf16 plans hand bf16 activations to the MFMA layers reading them (joins, row steps and
+            # QuantizeLinear pass them on / read them in the same dtype); fp32 plans stay f32
+            dt = (torch.bfloat16 if (s.kind in ("dense", "qdense", "dequant", "gru", "lstm", "join", "row")
+                                     and feeds_mma and plan.precision == "bf16")
                   else torch.float32)
-            self.step_out.append(torch.zeros((B, s.out_width), dtype=dt, device=self.device))
+            if step_qtype(s) is not None:
+                # quantised bytes: rows padded to 16 so qgemm loads and stores them as 16-byte vectors
+                self.step_out.append(torch.zeros((B, -(-s.out_width // 16) * 16), dtype=torch.int8, device=self.device))
+            else:
+                self.step_out.append(torch.zeros((B, s.out_width), dtype=dt, device=self.device))
             if s.kind == "tree":
                 need = 0
                 for b in self.buckets:
@@ -244,6 +249,12 @@ class DeviceModel:
                 fused_partial = None
             elif s.kind == "dense":
                 K.dense(cur, s.w, s.b, out, bucket, s.n, s.k, act=s.act, m_ptr=m_ptr)
+            elif s.kind == "qdense":  # int8 MFMA on the quantised bytes of the producing step
+                K.qdense(cur, s.w8, s.corr, s.mult, s.b, out, bucket, s.n, s.k, act=s.act, out_q=s.out_q, m_ptr=m_ptr)
+            elif s.kind == "quant":
+                K.quantize(cur, out, bucket, s.width, s.scale, s.zp, s.qtype, m_ptr=m_ptr)
+            elif s.kind == "dequant":
+                K.dequantize(cur, out, bucket, s.width, s.scale, s.zp, s.qtype, m_ptr=m_ptr)
             elif s.kind == "head":
                 K.mlp_head(s, cur, out, bucket, m_ptr=m_ptr, tree_partial=fused_partial,
                            ens=ens if i == len(steps) - 1 else None)

@@ -117,7 +117,7 @@ def plan_importance(plan, width: int) -> Dict[str, float]:
                 feat = meta[real] & 0xFFFF
             score += np.bincount(feat.astype(np.int64), minlength=width)[:width]
     else:
-        first = next((s for s in plan.steps if s.kind in ("dense", "head")), None)
+        first = next((s for s in plan.steps if s.kind in ("dense", "qdense", "head")), None)
         if first is not None:
             w = first.w1_np if first.kind == "head" else first.w_np   # [N, K]
             score[:min(width, w.shape[1])] = np.abs(w).sum(axis=0)[:width]

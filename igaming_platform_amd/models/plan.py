@@ -26,6 +26,24 @@ steps:
                  a join, a tree, another activation) -> ``row_op`` (csrc/kernels/rowops.hip).
                  A Softmax over the two logits of an exclusive dense layer is narrowed to
                  sigmoid(z1 - z0) instead, so a two-logit classifier runs on the fused head.
+* QDQ int8-quantised models (the standard ai.onnx format of ORT's static quantiser and of QAT
+  exports; opset 10 and 13 forms) lower to three step kinds, none of which depends on ``precision``:
+  ``QDenseStep``   DequantizeLinear(a) -> Gemm / MatMul on a DequantizeLinear-ed int8 / uint8
+                   initializer (per tensor, or per output channel on either axis, so ``transB``
+                   works), bias as a DequantizeLinear-ed int32 initializer, a float initializer or
+                   MatMul + Add, ``alpha`` / ``beta`` folded, a Relu / Sigmoid / Tanh and a
+                   following QuantizeLinear (when it is the only reader) in the epilogue -> K3
+                   ``qgemm`` on the i8 matrix cores (csrc/kernels/qgemm.hip); :func:`qdense_tables`
+                   builds its host tables. The output is the requantised bytes, else f32 (bf16
+                   under the runner's rule for bf16 plans).
+  ``QuantStep`` / ``DequantStep``  the two ops on their own (``quantize_rows`` /
+                   ``dequantize_rows``): a Q at the model input, after a tree, a join, a row op or
+                   on a value with other readers; a DQ that feeds anything but a quantised Gemm. So
+                   any float sub-graph lowered here may sit between a DQ and a Q.
+  Limits: scales and zero points are initializers; activations are quantised per tensor;
+  ``w_q - z_w`` must fit int8; K <= 32768 (the int32 accumulator bound). The QOperator format
+  (QLinearMatMul ...), MatMulInteger / DynamicQuantizeLinear, ``block_size``, 4-bit / 16-bit /
+  float8 types and ``saturate=0`` raise :class:`PlanError`.
 * ``BatchNormalization`` (inference) is a per-column affine and folds like ``Scaler``;
   ``Dropout`` is folded away.
 * ai.onnx.ml ``LinearClassifier`` / ``LinearRegressor`` (post NONE / LOGISTIC; a two-class
@@ -276,6 +294,10 @@ class Plan:
                 parts.append(f"{s.op}(#{s.a},#{s.b})")
             elif s.kind == "row":
                 parts.append(f"{s.act if s.op == 'act' else s.op}({s.width})")
+            elif s.kind == "qdense":
+                parts.append(f"qdense({s.x_type}:{s.k}->{s.n},{s.act},{s.out_q[2] if s.out_q else 'f32'})")
+            elif s.kind in ("quant", "dequant"):
+                parts.append(f"{s.kind}({s.width},{s.qtype})")
             else:
                 parts.append(f"{s.kind}(I={s.in_dim},H={s.hidden}{',lens' if getattr(s, 'masked', False) else ''})")
         return " -> ".join(parts)
@@ -322,6 +344,110 @@ class RowStep:
         return self.width
 
 
+ONNX_UINT8, ONNX_INT8 = 2, 3
+QTYPES = {ONNX_UINT8: "uint8", ONNX_INT8: "int8"}   # quantised element types (by the zero point's type)
+Q_OFF = {"uint8": 128, "int8": 0}      # the device stores a quantised value q as the signed byte q - off
+Q_RANGE = {"uint8": (0, 255), "int8": (-128, 127)}
+Q_MAX_K = 32768                        # qgemm: acc + corr stays inside int32 up to this reduction length
+QDQ_ONLY = ("quantised models are lowered in the QDQ format (QuantizeLinear / DequantizeLinear around float "
+            "Gemm / MatMul)")
+
+
+@dataclass
+class QDenseStep:
+    """DequantizeLinear(a) -> Gemm | MatMul on a ``DequantizeLinear``-ed int8 / uint8 weight, with an
+    optional Relu / Sigmoid / Tanh and an optional following QuantizeLinear folded in (K3 ``qgemm``,
+    csrc/kernels/qgemm.hip): reads the quantised activation bytes, accumulates in int32, writes
+    f32 / bf16 or the requantised bytes (``out_q``). None of it depends on ``precision``."""
+    n: int
+    k: int
+    act: str
+    wq_np: np.ndarray            # [N, K] int32: w_q - z_w (inside int8)
+    w_scale: np.ndarray          # [N] f32 (a per-tensor scale broadcast)
+    alpha: float                 # Gemm alpha (into mult)
+    x_scale: np.float32
+    x_zp: int
+    x_type: str                  # uint8 | int8
+    w_np: np.ndarray             # [N, K] f32 dequantised (x alpha), for plan_importance
+    b_np: Optional[np.ndarray]   # [N] f32 (Gemm C x beta, an Add constant; dequantised when it was int32)
+    out_q: Optional[Tuple[np.float32, int, str]] = None   # folded QuantizeLinear: (s_y, z_y, type)
+    w8: Any = None               # device tables (qdense_tables)
+    corr: Any = None
+    mult: Any = None
+    b: Any = None
+    kind: str = "qdense"
+    src: Optional[int] = None
+
+    @property
+    def out_width(self) -> int:
+        return self.n
+
+
+@dataclass
+class QuantStep:
+    """QuantizeLinear on its own (``quantize_rows``): f32 / bf16 -> stored bytes, per tensor."""
+    width: int
+    scale: np.float32
+    zp: int
+    qtype: str
+    kind: str = "quant"
+    src: Optional[int] = None
+
+    @property
+    def out_width(self) -> int:
+        return self.width
+
+
+@dataclass
+class DequantStep:
+    """DequantizeLinear on its own (``dequantize_rows``): stored bytes -> f32 / bf16, per tensor."""
+    width: int
+    scale: np.float32
+    zp: int
+    qtype: str
+    kind: str = "dequant"
+    src: Optional[int] = None
+
+    @property
+    def out_width(self) -> int:
+        return self.width
+
+
+def step_qtype(s) -> Optional[str]:
+    """The quantised type of a step's output buffer (None: a float buffer)."""
+    if s.kind == "quant":
+        return s.qtype
+    if s.kind == "qdense" and s.out_q is not None:
+        return s.out_q[2]
+    return None
+
+
+def qdense_tables(s: QDenseStep) -> Dict[str, Any]:
+    """Host tables of a quantised dense layer, as torch tensors on the CPU (no GPU needed):
+
+    * ``w8``   int8 [N_pad(128), K_pad(64)]: w_q - z_w, zero padded;
+    * ``corr`` int32 [N]: (off_x - z_x) * sum_k w8[n, k] (the device reads x as q_x - off_x);
+    * ``mult`` f32 [N]: s_x * s_w[n] * alpha, formed in float64 and rounded once;
+    * ``bias`` f32 [N] (zeros when the layer has none).
+
+    With them acc[m, n] = sum_k (q_x - off_x) w8[n, k] gives the layer's value as
+    float(acc + corr[n]) * mult[n] + bias[n]."""
+    import torch
+    n, k = s.wq_np.shape
+    if k > Q_MAX_K:
+        raise PlanError(f"quantised dense layer: K = {k} exceeds {Q_MAX_K} (the int32 accumulator bound)")
+    wq = s.wq_np.astype(np.int64)
+    if wq.min(initial=0) < -128 or wq.max(initial=0) > 127:
+        raise PlanError("quantised dense layer: w_q - z_w leaves [-128, 127]")
+    w8 = np.zeros((-(-n // 128) * 128, -(-k // 64) * 64), np.int8)
+    w8[:n, :k] = wq
+    corr = (Q_OFF[s.x_type] - int(s.x_zp)) * wq.sum(axis=1)
+    mult = (np.float64(s.x_scale) * s.w_scale.astype(np.float64) * np.float64(s.alpha)).astype(np.float32)
+    bias = np.zeros(n, np.float32) if s.b_np is None else np.ascontiguousarray(s.b_np, np.float32)
+    return dict(w8=torch.from_numpy(w8), corr=torch.from_numpy(corr.astype(np.int32)),
+                mult=torch.from_numpy(np.array(np.broadcast_to(mult, (n,)))), bias=torch.from_numpy(np.array(bias)))
+
+
 def step_inputs(steps, i: int) -> Tuple[int, ...]:
     """Indices of the steps whose outputs step ``i`` reads (-1: the model input)."""
     s = steps[i]
@@ -354,6 +480,11 @@ class _Val:
     label: bool = False       # a classifier's label output (not lowered)
     gru_y: bool = False       # a GRU's / LSTM's per-step outputs Y (only another such layer reads them)
     bidir_pending: bool = False  # a layout-0 bidirectional Y_h still in [D, N, H] order
+    # QDQ: a QuantizeLinear output (the step's buffer holds the bytes) ...
+    quant: Optional[Tuple[np.float32, int, str]] = None   # (scale, zero point, type)
+    # ... and a DequantizeLinear of one, not yet materialised: a quantised Gemm reads the bytes of
+    # ``step`` directly, any other reader gets a DequantStep first
+    deq: Optional[Tuple[np.float32, int, str]] = None
 
 
 ALIAS_OPS = ("Identity", "Flatten", "Squeeze", "Unsqueeze", "Reshape", "ZipMap", "Cast", "Dropout")
@@ -392,10 +523,14 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
     dims = in_vi[2]
     seq_input = len(dims) == 3
     in_width = int(dims[-1]) if dims and dims[-1] > 0 else -1
-    inits = set(model.initializer_names())
+    raw_inits = set(model.initializer_names())
+    # constants: the initializers, plus every DequantizeLinear of one (added as it is lowered)
+    inits = set(raw_inits)
+    fconst: Dict[str, np.ndarray] = {}    # DequantizeLinear(initializer) -> the f32 constant
+    qconst: Dict[str, Dict[str, Any]] = {}  # ... and its integer form: d = q - z, scale, axis, type
 
     def const(name):
-        return model.initializer(name)
+        return fconst[name] if name in fconst else model.initializer(name)
 
     # the nodes the output depends on, in dependency order: a depth-first post-order from the
     # output, so each branch's nodes stay contiguous (a dense layer and the N=1 layer reading it
@@ -488,6 +623,11 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
         if v.gru_y:
             cell = steps[v.step].kind.upper()
             raise PlanError(f"{what}: a {cell}'s per-step outputs are lowered only into another {cell} layer")
+        if v.quant is not None:
+            raise PlanError(f"{what}: a quantised tensor is read only by DequantizeLinear")
+        if v.deq is not None:   # a reader other than a quantised Gemm: the DequantizeLinear runs on its own
+            i = emit(DequantStep(v.width, *v.deq), v.step)
+            v = vals[name] = _Val(i, v.width, ml_col=v.ml_col, cpu_col=v.cpu_col)
         return v
 
     def plain(name, what) -> _Val:
@@ -556,6 +696,108 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
         op, a = n["op_type"], n["attrs"]
         ins = n["inputs"]
         x = ins[0] if ins else ""
+        if op in ("QLinearMatMul", "QLinearConv", "QLinearAdd", "QGemm", "MatMulInteger", "ConvInteger",
+                  "DynamicQuantizeLinear"):
+            raise PlanError(f"op {op} is not lowered to the device: {QDQ_ONLY}")
+        if op in ("QuantizeLinear", "DequantizeLinear"):
+            out = n["outputs"][0]
+            if int(a.get("block_size", 0)):
+                raise PlanError(f"{op}: block_size (blocked quantisation) is not lowered")
+            if int(a.get("saturate", 1)) != 1:
+                raise PlanError(f"{op}: saturate=0 is not lowered")
+            od = int(a.get("output_dtype", 0))
+            if od not in (0, ONNX_UINT8, ONNX_INT8):
+                raise PlanError(f"{op}: output_dtype {od} is not lowered (uint8 and int8 only)")
+            has_zp = len(ins) > 2 and bool(ins[2])
+            if len(ins) < 2 or ins[1] not in raw_inits or (has_zp and ins[2] not in raw_inits):
+                raise PlanError(f"{op}: scale and zero point must be constants (initializers)")
+            if int(model.initializer_dtype(ins[1])) != 1:
+                raise PlanError(f"{op}: the scale must be a float32 tensor")
+            sc = np.asarray(model.initializer(ins[1]), np.float32).ravel()
+            zp = np.asarray(model.initializer(ins[2]), np.int64).ravel() if has_zp else np.zeros(sc.size, np.int64)
+            zt = int(model.initializer_dtype(ins[2])) if has_zp else 0
+            if zp.size != sc.size or sc.size < 1 or not (sc > 0).all():
+                raise PlanError(f"{op}: scale (positive) and zero point must have the same size")
+            if op == "DequantizeLinear" and x in raw_inits:
+                # a constant: int8 / uint8 weights, an int32 bias; per-axis scales allowed
+                xt = int(model.initializer_dtype(x))
+                if xt not in (ONNX_UINT8, ONNX_INT8, ONNX_INT32):
+                    raise PlanError(f"DequantizeLinear: a constant of ONNX type {xt} is not lowered (uint8, int8, int32)")
+                if has_zp and zt != xt:
+                    raise PlanError("DequantizeLinear: the zero point's type differs from the tensor's")
+                q = np.asarray(model.initializer(x), np.int64)
+                axis, shape = None, [1] * q.ndim
+                if sc.size != 1:
+                    axis = int(a.get("axis", 1))
+                    axis += q.ndim if axis < 0 else 0
+                    if not 0 <= axis < q.ndim or q.shape[axis] != sc.size:
+                        raise PlanError(f"DequantizeLinear: {sc.size} scales do not match axis {axis} of shape {q.shape}")
+                    shape[axis] = sc.size
+                d = q - zp.reshape(shape)
+                fconst[out] = (d.astype(np.float64) * sc.astype(np.float64).reshape(shape)).astype(np.float32)
+                qconst[out] = dict(d=d, scale=sc, axis=axis, xt=xt)
+                inits.add(out)
+                continue
+            if sc.size != 1:
+                raise PlanError(f"{op}: per-axis quantisation of activations is not lowered")
+            if op == "QuantizeLinear":
+                qt = QTYPES.get(zt if has_zp else (od or ONNX_UINT8))
+                if qt is None or (od and has_zp and od != zt):
+                    raise PlanError(f"QuantizeLinear: zero point of ONNX type {zt} is not lowered (uint8 and int8 only)")
+                if not Q_RANGE[qt][0] <= int(zp[0]) <= Q_RANGE[qt][1]:
+                    raise PlanError("QuantizeLinear: the zero point lies outside its type")
+                v = plain(x, op)
+                if v.width <= 0:
+                    raise PlanError("QuantizeLinear: the width of its input must be known")
+                qi = (sc[0], int(zp[0]), qt)
+                st = steps[v.step] if v.step >= 0 else None
+                if (st is not None and st.kind == "qdense" and st.out_q is None and v.exclusive and single_use(x)):
+                    st.out_q, idx = qi, v.step    # requantisation in the layer's epilogue
+                else:   # at the model input, after a tree / join / row op, or on a value with other readers
+                    idx = emit(QuantStep(v.width, *qi), v.step)
+                vals[out] = _Val(idx, v.width, ml_col=v.ml_col, cpu_col=v.cpu_col, quant=qi)
+                continue
+            v = vals.get(x)
+            if v is None or v.quant is None:
+                raise PlanError("DequantizeLinear: lowered on an initializer or on a QuantizeLinear output")
+            if has_zp and QTYPES.get(zt) != v.quant[2]:
+                raise PlanError("DequantizeLinear: the zero point's type differs from the quantised tensor's")
+            if not Q_RANGE[v.quant[2]][0] <= int(zp[0]) <= Q_RANGE[v.quant[2]][1]:
+                raise PlanError("DequantizeLinear: the zero point lies outside its type")
+            vals[out] = _Val(v.step, v.width, ml_col=v.ml_col, cpu_col=v.cpu_col, deq=(sc[0], int(zp[0]), v.quant[2]))
+            continue
+        if op in ("Gemm", "MatMul") and len(ins) > 1 and ins[1] in qconst and x in vals and vals[x].deq is not None:
+            qc, v = qconst[ins[1]], vals[x]
+            tb = op == "Gemm" and bool(int(a.get("transB", 0)))
+            if op == "Gemm" and int(a.get("transA", 0)):
+                raise PlanError("Gemm transA=1 is not lowered")
+            # a scale per output channel (or one): anything else runs as a float layer on the dequantised weight
+            if qc["xt"] in QTYPES and qc["d"].ndim == 2 and qc["axis"] in (None, 0 if tb else 1):
+                d = qc["d"] if tb else qc["d"].T                    # [N, K]
+                N_, K_ = int(d.shape[0]), int(d.shape[1])
+                if v.width > 0 and K_ != v.width:
+                    raise PlanError(f"{op}: weight rows {K_} != input width {v.width}")
+                if d.min(initial=0) < -128 or d.max(initial=0) > 127:
+                    raise PlanError(f"{op}: the quantised weight minus its zero point leaves [-128, 127]")
+                if K_ > Q_MAX_K:
+                    raise PlanError(f"{op}: a quantised layer with K = {K_} > {Q_MAX_K} is not lowered")
+                alpha = float(a.get("alpha", 1.0)) if op == "Gemm" else 1.0
+                b = None
+                if op == "Gemm" and len(ins) > 2 and ins[2]:
+                    if ins[2] not in inits:
+                        raise PlanError("Gemm: bias must be an initializer (or a DequantizeLinear of one)")
+                    b = np.asarray(const(ins[2]), np.float32).ravel() * np.float32(a.get("beta", 1.0))
+                    if b.size == 1 and N_ > 1:
+                        b = np.full(N_, b[0], np.float32)
+                    if b.size != N_:
+                        raise PlanError("Gemm: bias length differs from the output width")
+                wf = fconst[ins[1]] if tb else fconst[ins[1]].T
+                idx = emit(QDenseStep(n=N_, k=K_, act="none", wq_np=np.ascontiguousarray(d, np.int32),
+                                      w_scale=np.ascontiguousarray(np.broadcast_to(qc["scale"], (N_,)), np.float32),
+                                      alpha=alpha, x_scale=v.deq[0], x_zp=v.deq[1], x_type=v.deq[2],
+                                      w_np=np.ascontiguousarray(wf * np.float32(alpha), np.float32), b_np=b), v.step)
+                vals[n["outputs"][0]] = _Val(idx, N_)
+                continue
         if op in ("TreeEnsembleClassifier", "TreeEnsembleRegressor", "TreeEnsemble"):
             # the opset-5 TreeEnsemble compiles to the same Ensemble (no label output, no base values)
             v = plain(x, op)
@@ -640,7 +882,8 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
             first = ins[0] == xd
             v = get(xd, op)
             st = steps[v.step] if v.step >= 0 else None
-            if (op == "Add" and v.scale is None and st is not None and st.kind == "dense" and st.act == "none"
+            if (op == "Add" and v.scale is None and st is not None and st.kind in ("dense", "qdense")
+                    and st.act == "none" and getattr(st, "out_q", None) is None
                     and v.exclusive and single_use(xd) and cst.size in (1, st.n)):
                 # MatMul + Add (and any constant added to a linear layer): the layer's bias
                 b = np.zeros(st.n) if st.b_np is None else st.b_np.astype(np.float64)
@@ -688,7 +931,8 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
         if op in ACT_OPS:
             v = plain(x, op)
             st = steps[v.step] if v.step >= 0 else None
-            if st is not None and st.kind == "dense" and st.act == "none" and v.exclusive and single_use(x):
+            if (st is not None and st.kind in ("dense", "qdense") and st.act == "none"
+                    and getattr(st, "out_q", None) is None and v.exclusive and single_use(x)):
                 st.act = op.lower()
             elif (st is not None and st.kind == "tree" and op == "Sigmoid" and st.post == 0 and st.binary_class < 0
                   and v.exclusive and single_use(x)):
@@ -944,8 +1188,10 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
         raise PlanError(f"op {op} is not lowered to the device")
 
     fv = vals.get(output_name)
-    if fv is None or fv.label:
+    if fv is None or fv.label or fv.quant is not None:
         raise PlanError("the primary output must be a score / probability tensor")
+    if fv.deq is not None:
+        fv = get(output_name, "output")   # a trailing Q -> DQ: the DequantizeLinear is the last step
     if fv.scale is not None:
         fv = plain(output_name, "output")
     if not steps or fv.step != len(steps) - 1:
@@ -1163,6 +1409,9 @@ def to_device(plan: Plan, device, precision: str = "fp32") -> Plan:
             s.w1 = (_f32_padded(s.w1_np, k_mult=32) if precision == "fp32" else pad(s.w1_np)).to(device)
             s.b1 = None if s.b1_np is None else torch.from_numpy(np.ascontiguousarray(s.b1_np)).to(device)
             s.w2 = torch.from_numpy(s.w2_np).to(device)
+        elif s.kind == "qdense":
+            t = qdense_tables(s)
+            s.w8, s.corr, s.mult, s.b = (t[k].to(device) for k in ("w8", "corr", "mult", "bias"))
         elif s.kind == "row":
             s.gamma, s.beta = (None if t is None else torch.from_numpy(np.ascontiguousarray(t, np.float32)).to(device)
                                for t in (s.gamma_np, s.beta_np))

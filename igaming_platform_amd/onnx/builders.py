@@ -465,7 +465,113 @@ def tabular_resnet(n_features: int = 32, width: int = 128, blocks: int = 2, norm
                  metadata={"family": "mlp", "blocks": str(blocks), "norm": norm})
 
 
-BUILDERS = {"logistic": logistic, "gbdt": gbdt, "gbdt_v5": gbdt_v5, "stacked": stacked, "ltv_mlp": ltv_mlp, "gru": gru,
+def _qparams(lo: float, hi: float, int8: bool, pow2: bool):
+    """(scale, zero point) of an asymmetric 8-bit range that holds [lo, hi] and zero, as ORT's static
+    quantiser derives them from calibration; ``pow2`` rounds the scale to a power of two."""
+    lo, hi = min(float(lo), 0.0), max(float(hi), 0.0)
+    qmin, qmax = (-128, 127) if int8 else (0, 255)
+    scale = max(hi - lo, 1e-6) / (qmax - qmin)
+    if pow2:
+        scale = 2.0 ** round(np.log2(scale))
+    zp = int(np.clip(np.rint(qmin - lo / scale), qmin, qmax))
+    return np.float32(scale), zp
+
+
+def qdq_mlp(widths=(30, 64, 1), seed: int = 15, act_int8: bool = False, per_channel: bool = False,
+            bias: str = "int32", pow2: bool = False, w_uint8: bool = False, out_qdq: bool = False,
+            hidden_act: str = "Relu", transB: bool = False, opset: int = 13, calib_rows: int = 512,
+            clip: float = 0.97, family: str = "mlp"):
+    """A random float MLP quantised the way ORT's static quantiser writes it (QDQ format):
+
+        input -> Q -> DQ -> Gemm(DQ(W), DQ(b)) -> ``hidden_act`` -> Q -> DQ -> ... -> Gemm -> Sigmoid
+
+    ``widths``: input, hidden ..., output (1). Activations are uint8 (``act_int8``: int8), weights
+    int8 with zero point 0, per tensor or per output channel (``per_channel``; ``w_uint8``: uint8
+    with zero point 128). ``bias``: ``int32`` (quantised, through DequantizeLinear), ``float`` (a
+    float initializer) or ``add`` (MatMul + Add of the dequantised int32 bias). ``transB`` stores
+    the weights [N, K]. ``pow2`` rounds every scale to a power of two (all arithmetic is then
+    exact in f32). ``out_qdq`` appends a Q -> DQ pair to the output. ``opset`` 10 writes the
+    attribute-free per-tensor form. Activation ranges come from a calibration pass over random
+    inputs: each range covers the ``clip`` quantile, so a few per cent of the values saturate."""
+    if bias not in ("int32", "float", "add"):
+        raise ValueError("bias: int32, float or add")
+    if opset < 13 and per_channel:
+        raise ValueError("per-channel scales need the opset-13 axis attribute")
+    if bias == "add" and transB:
+        raise ValueError("MatMul has no transB")
+    rng = np.random.default_rng(seed)
+    widths = [int(w) for w in widths]
+    ws = [(rng.standard_normal((k, n)) * np.sqrt(2.0 / k)).astype(np.float32) for k, n in zip(widths, widths[1:])]
+    bs = [(rng.standard_normal(n) * 0.1).astype(np.float32) for n in widths[1:]]
+    calib = rng.uniform(-1.0, 2.0, (calib_rows, widths[0])).astype(np.float32)
+    zp_dt = np.int8 if act_int8 else np.uint8
+    nodes, inits = [], []
+
+    def act_q(x: str, name: str, h: np.ndarray):
+        """Q -> DQ on ``x`` with the range of the calibration values ``h``; returns the DQ output."""
+        s, z = _qparams(np.quantile(h, 1.0 - clip), np.quantile(h, clip), act_int8, pow2)
+        inits.extend([tensor(f"{name}_scale", np.array(s, np.float32)), tensor(f"{name}_zp", np.array(z, zp_dt))])
+        nodes.extend([node("QuantizeLinear", [x, f"{name}_scale", f"{name}_zp"], [f"{name}_q"]),
+                      node("DequantizeLinear", [f"{name}_q", f"{name}_scale", f"{name}_zp"], [f"{name}_dq"])])
+        q = np.clip(np.rint(h / s) + z, *((-128, 127) if act_int8 else (0, 255)))
+        return f"{name}_dq", s, ((q - z) * s).astype(np.float32)
+
+    cur, s_x, h = act_q("input", "x0", calib)
+    for i, (w, b) in enumerate(zip(ws, bs)):
+        last = i == len(ws) - 1
+        amax = np.abs(w).max(axis=0 if per_channel else None)
+        s_w = np.maximum(amax, 1e-6) / 127.0
+        if pow2:
+            s_w = 2.0 ** np.ceil(np.log2(s_w))
+        s_w = np.asarray(s_w, np.float32)
+        wq = np.clip(np.rint(w / s_w), -127, 127).astype(np.int64)          # [K, N]
+        w_dq = (wq * s_w).astype(np.float32)
+        z_w = 128 if w_uint8 else 0
+        w_store = (wq + z_w).astype(np.uint8 if w_uint8 else np.int8)
+        axis = 1
+        if transB:
+            w_store, axis = np.ascontiguousarray(w_store.T), 0
+        ax = dict(axis=axis) if per_channel else {}
+        inits.extend([tensor(f"W{i}_q", w_store), tensor(f"W{i}_scale", s_w),
+                      tensor(f"W{i}_zp", np.full(s_w.shape, z_w, w_store.dtype))])
+        nodes.append(node("DequantizeLinear", [f"W{i}_q", f"W{i}_scale", f"W{i}_zp"], [f"W{i}_dq"], **ax))
+        b_dq = b
+        if bias != "float":
+            s_b = (np.float64(s_x) * s_w.astype(np.float64)).astype(np.float32)
+            bq = np.rint(b / s_b).astype(np.int32)
+            b_dq = (bq * s_b.astype(np.float64)).astype(np.float32)
+            s_b = np.broadcast_to(s_b, (widths[i + 1],)) if per_channel else s_b
+            inits.extend([tensor(f"B{i}_q", bq), tensor(f"B{i}_scale", np.ascontiguousarray(s_b, np.float32))])
+            nodes.append(node("DequantizeLinear", [f"B{i}_q", f"B{i}_scale"], [f"B{i}_dq"],
+                              **(dict(axis=0) if per_channel else {})))
+        else:
+            inits.append(tensor(f"B{i}_dq", b))
+        if bias == "add":
+            nodes.extend([node("MatMul", [cur, f"W{i}_dq"], [f"m{i}"]), node("Add", [f"m{i}", f"B{i}_dq"], [f"z{i}"])])
+        else:
+            nodes.append(node("Gemm", [cur, f"W{i}_dq", f"B{i}_dq"], [f"z{i}"], **(dict(transB=1) if transB else {})))
+        z = h.astype(np.float64) @ w_dq.astype(np.float64) + b_dq
+        if last:
+            nodes.append(node("Sigmoid", [f"z{i}"], ["prob" if out_qdq else "output"]))
+            h = 1.0 / (1.0 + np.exp(-z))
+        else:
+            attrs = dict(alpha=0.125) if hidden_act == "LeakyRelu" else {}
+            nodes.append(node(hidden_act, [f"z{i}"], [f"a{i}"], **attrs))
+            h = {"Relu": lambda v: np.maximum(v, 0), "LeakyRelu": lambda v: np.where(v > 0, v, 0.125 * v),
+                 "Tanh": np.tanh, "Sigmoid": lambda v: 1.0 / (1.0 + np.exp(-v))}[hidden_act](z).astype(np.float32)
+            cur, s_x, h = act_q(f"a{i}", f"x{i + 1}", h)
+    if out_qdq:
+        s, z = (np.float32(2.0 ** -8), -128 if act_int8 else 0)
+        inits.extend([tensor("out_scale", np.array(s, np.float32)), tensor("out_zp", np.array(z, zp_dt))])
+        nodes.extend([node("QuantizeLinear", ["prob", "out_scale", "out_zp"], ["out_q"]),
+                      node("DequantizeLinear", ["out_q", "out_scale", "out_zp"], ["output"])])
+    return model(nodes, [value_info("input", S.FLOAT, ["N", widths[0]])],
+                 [value_info("output", S.FLOAT, ["N", widths[-1]])], inits, name="qdq_mlp", opset=opset,
+                 metadata={"family": family, "format": "qdq", "layers": str(len(ws))})
+
+
+BUILDERS = {"qdq_mlp": qdq_mlp,
+            "logistic": logistic, "gbdt": gbdt, "gbdt_v5": gbdt_v5, "stacked": stacked, "ltv_mlp": ltv_mlp, "gru": gru,
             "lstm": lstm, "torch_mlp": torch_mlp, "tabular_resnet": tabular_resnet,
             "sklearn_linear": sklearn_linear, "linear_regressor": linear_regressor,
             "mlp_classifier": mlp_classifier, "wide_deep": wide_deep, "residual_mlp": residual_mlp}

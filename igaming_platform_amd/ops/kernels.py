@@ -357,6 +357,83 @@ def dense(X: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], Y: tor
         _mod().gemm(d, _stream())
 
 
+Q_OFF = {"uint8": 128, "int8": 0}   # a quantised value q is stored as the signed byte q - off
+Q_MAX_K = 32768
+
+
+def _qparams(what: str, scale, zp: int, qtype: str):
+    if qtype not in Q_OFF:
+        raise ValueError(f"{what}: quantised type must be uint8 or int8")
+    off = Q_OFF[qtype]
+    if not float(scale) > 0 or not off - 128 <= int(zp) <= off + 127:
+        raise ValueError(f"{what}: scale must be positive and the zero point inside {qtype}")
+    return float(scale), int(zp), off
+
+
+def qdense(X: torch.Tensor, w8: torch.Tensor, corr: torch.Tensor, mult: torch.Tensor, bias: Optional[torch.Tensor],
+           Y: torch.Tensor, M: int, N: int, K: int, act: str = "none", out_q=None,
+           m_ptr: Optional[torch.Tensor] = None) -> None:
+    """Quantised dense layer (qgemm.hip): X int8 [rows, ldx] holds the stored bytes q_x - off_x,
+    ``w8`` / ``corr`` / ``mult`` / ``bias`` are models.plan.qdense_tables. Y[:M, :N] =
+    act(float(acc + corr) * mult + bias) as float32 / bfloat16, or with ``out_q`` = (scale, zero
+    point, "uint8" | "int8") the requantised stored bytes in an int8 ``Y``."""
+    dev = X.device
+    if X.dtype != torch.int8 or X.dim() != 2 or w8.dtype != torch.int8 or w8.dim() != 2:
+        raise ValueError("qdense: X and w8 must be 2-D int8")
+    if w8.shape[0] % 128 or w8.shape[1] % 64 or w8.shape[0] < N or w8.shape[1] < K:
+        raise ValueError("qdense: w8 must be padded to [N_pad % 128 == 0, K_pad % 64 == 0]")
+    if K < 1 or K > Q_MAX_K or N < 1 or M < 0:
+        raise ValueError(f"qdense: 1 <= K <= {Q_MAX_K}, N >= 1, M >= 0")
+    if Y.dim() != 2 or X.shape[1] < K or Y.shape[1] < N or X.shape[0] < M or Y.shape[0] < M:
+        raise ValueError("qdense: operand shapes smaller than M/N/K")
+    if corr.numel() < N or mult.numel() < N or (bias is not None and bias.numel() < N):
+        raise ValueError("qdense: corr / mult / bias shorter than N")
+    if out_q is None:
+        if Y.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("qdense: Y must be float32 or bfloat16 without out_q")
+        y_kind, ys, yz, yo = int(Y.dtype == torch.bfloat16), 1.0, 0, 0
+    else:
+        if Y.dtype != torch.int8:
+            raise ValueError("qdense: a requantised Y must be int8 (the stored bytes)")
+        ys, yz, yo = _qparams("qdense", *out_q)
+        y_kind = 2
+    d = dict(X=_need(X, "X", device=dev), W=_need(w8, "w8", device=dev),
+             corr=_need(corr, "corr", dtype=torch.int32, device=dev), mult=_need(mult, "mult", dtype=torch.float32, device=dev),
+             bias=_opt(bias, "bias", dtype=torch.float32, device=dev), Y=_need(Y, "Y", device=dev),
+             m_ptr=_opt(m_ptr, "m_ptr", dtype=torch.int32), M=int(M), N=int(N), K=int(K), ldx=int(X.shape[1]),
+             ldy=int(Y.shape[1]), ldw=int(w8.shape[1]), w_rows=int(w8.shape[0]), y_kind=y_kind, act=ACT[act],
+             y_scale=ys, y_zp=yz, y_off=yo)
+    _mod().qgemm(d, _stream())
+
+
+def _quant_rows(what: str, F: torch.Tensor, Q: torch.Tensor, M: int, N: int, scale, zp: int, qtype: str,
+                dequant: int, m_ptr: Optional[torch.Tensor]) -> None:
+    dev = Q.device
+    if F.dim() != 2 or F.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"{what}: the float tensor must be 2-D float32 or bfloat16")
+    if Q.dim() != 2 or Q.dtype != torch.int8:
+        raise ValueError(f"{what}: the quantised tensor must be 2-D int8 (the stored bytes)")
+    if N < 1 or M < 0 or F.shape[1] < N or Q.shape[1] < N or min(F.shape[0], Q.shape[0]) < M:
+        raise ValueError(f"{what}: operand shapes smaller than M / N")
+    s, z, off = _qparams(what, scale, zp, qtype)
+    d = dict(F=_need(F, "F", device=dev), Q=_need(Q, "Q", device=dev), m_ptr=_opt(m_ptr, "m_ptr", dtype=torch.int32),
+             M=int(M), N=int(N), ldf=int(F.shape[1]), ldq=int(Q.shape[1]), f_bf16=int(F.dtype == torch.bfloat16),
+             dequant=dequant, scale=s, zp=z, off=off)
+    _mod().quant_rows(d, _stream())
+
+
+def quantize(X: torch.Tensor, Y: torch.Tensor, M: int, N: int, scale, zp: int, qtype: str,
+             m_ptr: Optional[torch.Tensor] = None) -> None:
+    """QuantizeLinear (quantize_rows): Y[:M, :N] (int8) = clamp(rint(X / scale) + zp) - off."""
+    _quant_rows("quantize", X, Y, M, N, scale, zp, qtype, 0, m_ptr)
+
+
+def dequantize(X: torch.Tensor, Y: torch.Tensor, M: int, N: int, scale, zp: int, qtype: str,
+               m_ptr: Optional[torch.Tensor] = None) -> None:
+    """DequantizeLinear (dequantize_rows): Y[:M, :N] (f32 / bf16) = (X + off - zp) * scale."""
+    _quant_rows("dequantize", Y, X, M, N, scale, zp, qtype, 1, m_ptr)
+
+
 JOIN_OPS = {"add": 0, "concat": 1}
 
 
