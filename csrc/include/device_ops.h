@@ -9,15 +9,37 @@
 #pragma once
 #include <stdint.h>
 
-#define IGP_DEVICE_OPS_ABI 4
+#define IGP_DEVICE_OPS_ABI 5
 
 // bits of IgpDeviceOps::submit's want_features argument
 #define IGP_SUBMIT_WANT_FEATURES 1
 #define IGP_SUBMIT_NO_UPDATE 2
 
+// A step's rows read in place: at most IGP_ROW_SEGS runs of rows, each in host memory the device
+// reads itself (host_alloc below), instead of one packed copy in the slot's request buffer.
+// Sixteen covers one partial request from each of 16 ingress threads.
+#define IGP_ROW_SEGS 16
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+
+// One run of a step's rows: `count` ReqRec (48 bytes each) at the device-visible address `src`
+// (16-byte aligned) are the step's rows first .. first + count - 1. The runs of a table are in
+// row order and cover rows 0 .. n - 1 of the step without gaps.
+typedef struct IgpRowSeg {
+  uint64_t src;
+  int32_t first;
+  int32_t count;
+} IgpRowSeg;
+
+// The slot's segment table, next to its batch header in the request buffer. nseg == 0: the rows
+// are in the slot's request buffer (rows()), as for every caller that knows nothing of the table.
+typedef struct IgpRowSegTable {
+  int32_t nseg;
+  int32_t pad[3];
+  IgpRowSeg seg[IGP_ROW_SEGS];
+} IgpRowSegTable;
 
 typedef struct IgpDeviceOps {
   uint32_t abi;       // IGP_DEVICE_OPS_ABI
@@ -51,6 +73,18 @@ typedef struct IgpDeviceOps {
   // chunks back to back). The per-GPU D2H result path hands out a node-shared region laid out
   // [owner][sender][cap * W], so a sender's chunks are world * cap * W apart.
   int64_t res_owner_stride;
+  // In-place rows (optional, exchange == 0 only; any of the three null: the device has no such
+  // mode and every step is packed into rows()).
+  // host_alloc: `bytes` of host memory, 16-byte aligned, that the device reads in place (pinned
+  // for GPU devices); *dev_addr receives the address the device reads it at. Null on failure.
+  // host_free takes no ctx: it is a plain function of the device's module and stays callable for
+  // a buffer after the device object that allocated it is gone (a device swapped out while
+  // requests still hold their row buffers).
+  void* (*host_alloc)(void* ctx, uint64_t bytes, uint64_t* dev_addr);
+  void (*host_free)(void* p);
+  // the slot's segment table (host-writable; same validity as rows()). The caller sets nseg for
+  // EVERY step it submits once it has used the table: a slot keeps no state between steps.
+  IgpRowSegTable* (*row_segs)(void* ctx, int32_t slot);
 } IgpDeviceOps;
 
 #ifdef __cplusplus

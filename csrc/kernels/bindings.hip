@@ -72,6 +72,9 @@ UpdateArgs update_args(const py::dict& d) {
   a.dmax = geti(d, "dmax");
   a.region = geti(d, "region", DEDUP_STANDALONE);
   a.src = ptr<const char*>(d, "src");
+  a.segs = ptr<const IgpRowSegTable*>(d, "segs");
+  if (a.segs && (!a.src || (reinterpret_cast<uintptr_t>(a.segs) & 15)))
+    throw std::runtime_error("update args: a segment table goes with a slab source, 16-byte aligned");
   a.hll_lc = ptr<const int32_t*>(d, "hll_lc");
   if (!a.hll_lc) throw std::runtime_error("update args: hll_lc table required (cached HLL estimates)");
   a.xrecv = ptr<const ReqRec*>(d, "xrecv");

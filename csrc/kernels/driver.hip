@@ -130,6 +130,17 @@ class PipeDriver {
     host_feat_[slot] = reinterpret_cast<char*>(feat);
   }
 
+  // the slot's segment table (device_ops.h IgpRowSegTable) in pinned host memory, the one its
+  // dedup insert was built with (UpdateArgs::segs). Once every slot has one, device_ops() offers
+  // the serving core the in-place row mode; without, the core packs every step into the slab
+  void set_row_segs(int slot, uintptr_t table) {
+    if (slot < 0 || slot >= depth_) throw std::runtime_error("PipeDriver: bad slot");
+    if (!table || (table & 15)) throw std::runtime_error("PipeDriver: segment table must be 16-byte aligned");
+    if ((int)segs_.size() != depth_) segs_.assign(depth_, nullptr);
+    segs_[slot] = reinterpret_cast<IgpRowSegTable*>(table);
+    segs_[slot]->nseg = 0;
+  }
+
   // C function table for the native serving core (csrc/include/device_ops.h): the core issues
   // this pipeline's batches from its own threads (no Python, no GIL)
   uintptr_t device_ops() {
@@ -191,6 +202,31 @@ class PipeDriver {
     ops_.features = [](void* ctx, int32_t slot) -> const void* {
       return static_cast<PipeDriver*>(ctx)->host_feat_[slot];
     };
+    ops_.host_alloc = nullptr;
+    ops_.host_free = nullptr;
+    ops_.row_segs = nullptr;
+    if ((int)segs_.size() == depth_ && std::find(segs_.begin(), segs_.end(), nullptr) == segs_.end()) {
+      // request rows the dedup insert reads where the ingress threads wrote them: page-locked host
+      // memory of the process, mapped into the device's address space (no hipHostRegister of
+      // caller memory: registration costs more than the copy it would save)
+      ops_.host_alloc = [](void* ctx, uint64_t bytes, uint64_t* dev_addr) -> void* {
+        auto* d = static_cast<PipeDriver*>(ctx);
+        void* p = nullptr;
+        void* dp = nullptr;
+        if (hipSetDevice(d->device_) != hipSuccess) return nullptr;
+        if (hipHostMalloc(&p, size_t(bytes), hipHostMallocDefault) != hipSuccess) return nullptr;
+        if (hipHostGetDevicePointer(&dp, p, 0) != hipSuccess || (reinterpret_cast<uintptr_t>(dp) & 15)) {
+          (void)hipHostFree(p);
+          return nullptr;
+        }
+        *dev_addr = reinterpret_cast<uint64_t>(dp);
+        return p;
+      };
+      ops_.host_free = [](void* p) { (void)hipHostFree(p); };
+      ops_.row_segs = [](void* ctx, int32_t slot) -> IgpRowSegTable* {
+        return static_cast<PipeDriver*>(ctx)->segs_[slot];
+      };
+    }
     return reinterpret_cast<uintptr_t>(&ops_);
   }
 
@@ -234,6 +270,7 @@ class PipeDriver {
     if (it == graphs_.end()) throw std::runtime_error("PipeDriver: no graphs for this bucket/slot");
     Cmd c{slot, bucket, n, seq, now, rows, with_features, false, false, it->second};
     py::gil_scoped_release nogil;
+    if ((int)segs_.size() == depth_ && segs_[slot]) segs_[slot]->nseg = 0;  // this caller's rows are in the slab
     // the same bound the serving core passes down (device_ops.h IGP_SUBMIT_NO_UPDATE), over the
     // rows this call copies into the slab; rows already in the slab: no bound, the update runs
     // (computed in issue(), in the pass that copies them)
@@ -420,6 +457,7 @@ class PipeDriver {
   int64_t update_skips_ = 0, update_launches_ = 0;  // written by the issuing thread
   // native serving core interface
   std::vector<char*> host_res_, host_feat_;
+  std::vector<IgpRowSegTable*> segs_;  // by slot (set_row_segs)
   std::vector<int> buckets_;
   IgpDeviceOps ops_{};
   int device_ = 0;
@@ -441,6 +479,7 @@ void register_driver(py::module_& m) {
       .def(py::init<uintptr_t, uintptr_t, uintptr_t, int, py::list>())
       .def("set_graphs", &PipeDriver::set_graphs)
       .def("set_host_results", &PipeDriver::set_host_results)
+      .def("set_row_segs", &PipeDriver::set_row_segs)
       .def("device_ops", &PipeDriver::device_ops)
       .def("set_ops", &PipeDriver::set_ops)
       .def("set_state_update", &PipeDriver::set_state_update)

@@ -916,6 +916,8 @@ __global__ void __launch_bounds__(64) dedup_insert_list_kernel(UpdateArgs a) {
   const int i = blockIdx.x * 64 + lane;
   int2 r = make_int2(-1, 0);  // {slot, tx_type}
   int4 hv;
+  int nseg = 0;                            // in-place rows: live entries of the segment table
+  uint4 ent = make_uint4(0u, 0u, 0u, 0u);  // lane q + 1: entry q {src lo, src hi, first, count}; lane 0: {nseg}
   if (a.xrecv) {
     // rows-region exchange: compact this owner's chunk of every sender's block (host memory)
     // here instead of a separate compact kernel and a device round trip of the rows. Lane p < xn
@@ -963,8 +965,20 @@ __global__ void __launch_bounds__(64) dedup_insert_list_kernel(UpdateArgs a) {
   } else {
     // the batch header {n, seq, now}: from the host slab (every lane the same 16 bytes: one
     // request per wave) or the device copy
+    // the slot's segment table (device_ops.h IgpRowSegTable, nullable): with nseg > 0 the rows are
+    // not in the slab but in up to IGP_ROW_SEGS host buffers of the serving core's requests. One
+    // 16-byte read per lane, issued BEFORE the header's and waited for with it: lane 0 takes
+    // {nseg, pad}, lane q + 1 entry q. A row so stays two dependent reads from the host (header and
+    // table, then the row); read one after the other - count, entries, row - they were four and
+    // the kernel took 42 us instead of 29. (A per-lane address on purpose: a wave-uniform read of
+    // nseg becomes a scalar load, and the scalar cache is not coherent with the host's writes.)
+    if (a.src && a.segs && lane <= IGP_ROW_SEGS) ent = reinterpret_cast<const uint4*>(a.segs)[lane];
     hv = *reinterpret_cast<const int4*>(a.src ? reinterpret_cast<const void*>(a.src)
                                               : reinterpret_cast<const void*>(a.hdr));
+    if (a.src && a.segs) {
+      nseg = __builtin_amdgcn_readlane((int)ent.x, 0);
+      nseg = nseg < 0 ? 0 : (nseg > IGP_ROW_SEGS ? IGP_ROW_SEGS : nseg);
+    }
   }
   const int n = min(hv.x, a.n_max);  // as upd_n: the header's live count
   const int64_t now = (int64_t)(((uint64_t)(uint32_t)hv.w << 32) | (uint32_t)hv.z);
@@ -974,10 +988,31 @@ __global__ void __launch_bounds__(64) dedup_insert_list_kernel(UpdateArgs a) {
     // (rows, route and header written above)
   } else if (a.src) {
     if (i == 0) *reinterpret_cast<int4*>(const_cast<BatchHdr*>(a.hdr)) = hv;
+    // in-place rows: every lane takes the last table entry that starts at or before its row (the
+    // scan is wave-uniform, the choice per lane: a wave may straddle two or three segments)
+    const uint4* sp = reinterpret_cast<const uint4*>(a.src + sizeof(BatchHdr)) + 3 * (size_t)i;
+    bool have = live;
+    if (nseg > 0) {
+      int p = 0;
+#pragma unroll
+      for (int q = 1; q < IGP_ROW_SEGS; ++q)
+        if (q < nseg && (int)__builtin_amdgcn_readlane((int)ent.z, q + 1) <= i) p = q;
+      // (every lane takes part in the exchanges: entry p's lane, p + 1, may hold no live row itself)
+      const uint64_t base =
+          ((uint64_t)(uint32_t)__shfl((int)ent.y, p + 1, 64) << 32) | (uint32_t)__shfl((int)ent.x, p + 1, 64);
+      const int j = i - __shfl((int)ent.z, p + 1, 64);
+      const uint32_t cnt = (uint32_t)__shfl((int)ent.w, p + 1, 64);
+      have = live & ((uint32_t)j < cnt);  // never past a segment's end
+      sp = reinterpret_cast<const uint4*>(base) + 3 * (size_t)j;
+    }
     if (live) {
-      const uint4* sp = reinterpret_cast<const uint4*>(a.src + sizeof(BatchHdr)) + 3 * (size_t)i;
       uint4* dp = reinterpret_cast<uint4*>(const_cast<ReqRec*>(a.req + i));
-      const uint4 q0 = sp[0], q1 = sp[1], q2 = sp[2];
+      uint4 q0 = make_uint4(0xffffffffu, 0u, 0u, 0u), q1 = make_uint4(0u, 0u, 0u, 0u), q2 = q1;  // slot -1
+      if (have) {
+        q0 = sp[0];
+        q1 = sp[1];
+        q2 = sp[2];
+      }
       dp[0] = q0;
       dp[1] = q1;
       dp[2] = q2;

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../include/device_ops.h"
 #include "../include/records.h"
 #include "oplist.h"
 
@@ -53,7 +54,10 @@ struct UpdateArgs {
   // scorer dedup insert only (nullable): the pinned host slab [BatchHdr | ReqRec x n]; the kernel
   // reads the batch from it and writes the device copy (hdr, req) for the later stages
   const char* src;
-  const int32_t* hll_lc;    // [257] linear-counting table (the cached HLL estimates, AcctRT)
+  // with src only (nullable): the slot's segment table in pinned host memory. nseg > 0: the rows
+  // are not behind the slab's header but in the host buffers the table names (device_ops.h)
+  const IgpRowSegTable* segs;
+  const int32_t* hll_lc;   // [257] linear-counting table (the cached HLL estimates, AcctRT)
   // scorer dedup insert of the rows-region exchange only (nullable): the rows come from this
   // owner's chunk of every sender's block of the node-shared rows region (sender p's chunk at
   // xrecv + p * xpstride: header record {slot = count, ts = sender clock} + up to xc rows); the

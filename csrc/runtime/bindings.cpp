@@ -659,10 +659,14 @@ PYBIND11_MODULE(_native, m) {
       .def_property_readonly("rank", &StepClock::rank);
 
   py::class_<CpuDevice, std::shared_ptr<CpuDevice>>(m, "CpuDevice")
-      .def(py::init<std::shared_ptr<CpuScorer>, int, int>(), py::arg("scorer"), py::arg("depth") = 2,
-           py::arg("cap") = 8192, py::keep_alive<1, 2>())
+      .def(py::init<std::shared_ptr<CpuScorer>, int, int, bool>(), py::arg("scorer"), py::arg("depth") = 2,
+           py::arg("cap") = 8192, py::arg("inplace") = true, py::keep_alive<1, 2>())
       .def("device_ops", [](const CpuDevice& d) { return reinterpret_cast<uintptr_t>(d.ops()); })
-      .def("debug_fail_steps", &CpuDevice::debug_fail_steps, py::arg("n"), py::arg("after") = 0);
+      .def("debug_fail_steps", &CpuDevice::debug_fail_steps, py::arg("n"), py::arg("after") = 0)
+      .def("debug_hold_steps", &CpuDevice::debug_hold_steps, py::arg("n"))
+      .def("debug_release_steps", &CpuDevice::debug_release_steps, py::call_guard<py::gil_scoped_release>())
+      .def("debug_held_steps", &CpuDevice::debug_held_steps)
+      .def_property_readonly("gathered_steps", &CpuDevice::gathered_steps);
 
   py::class_<ShmXchgDevice, std::shared_ptr<ShmXchgDevice>>(m, "ShmXchgDevice")
       .def(py::init<std::shared_ptr<CpuScorer>, const std::string&, int, int, int, int, bool, double>(),
@@ -952,6 +956,8 @@ PYBIND11_MODULE(_native, m) {
         d["submit_ns"] = t.submit_ns; d["wait_errors"] = t.wait_errors; d["max_step_rows"] = t.max_step_rows;
         d["release_ns"] = t.release_ns; d["slot_wait_ns"] = t.slot_wait_ns; d["rows_wait_ns"] = t.rows_wait_ns;
         d["slot_waits"] = t.slot_waits; d["slot_wait_inflight"] = t.slot_wait_inflight;
+        d["inplace_steps"] = t.inplace_steps; d["packed_steps"] = t.packed_steps;
+        d["rowbufs"] = t.rowbufs; d["rowbufs_free"] = t.rowbufs_free;
         d["actions"] = py::make_tuple(t.actions[0], t.actions[1], t.actions[2], t.actions[3]);
         py::list dl;
         for (int k = 0; k < 11; ++k) dl.append(t.deciles[k]);

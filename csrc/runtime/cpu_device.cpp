@@ -3,6 +3,7 @@
 #include <unistd.h>
 
 #include <chrono>
+#include <cstdlib>
 #include <cstring>
 #include <stdexcept>
 #include <thread>
@@ -19,7 +20,7 @@ void set_err(char* err, int32_t errlen, const char* msg) {
 }  // namespace
 
 // ============================================================================ CpuDevice
-CpuDevice::CpuDevice(std::shared_ptr<CpuScorer> sc, int depth, int cap) : sc_(std::move(sc)) {
+CpuDevice::CpuDevice(std::shared_ptr<CpuScorer> sc, int depth, int cap, bool inplace) : sc_(std::move(sc)) {
   if (!sc_ || depth < 1 || cap < 1) throw std::runtime_error("CpuDevice: scorer / depth / capacity");
   slots_.resize(depth);
   for (auto& s : slots_) {
@@ -39,7 +40,22 @@ CpuDevice::CpuDevice(std::shared_ptr<CpuScorer> sc, int depth, int cap) : sc_(st
   ops_.wait = &wait_fn;
   ops_.results = &results_fn;
   ops_.features = &features_fn;
+  if (inplace) {
+    ops_.host_alloc = &host_alloc_fn;
+    ops_.host_free = &host_free_fn;
+    ops_.row_segs = &row_segs_fn;
+  }
 }
+
+void* CpuDevice::host_alloc_fn(void*, uint64_t bytes, uint64_t* dev_addr) {
+  void* p = std::aligned_alloc(64, (size_t(bytes) + 63) & ~size_t(63));
+  if (p) *dev_addr = reinterpret_cast<uint64_t>(p);  // this device reads host memory where it is
+  return p;
+}
+
+void CpuDevice::host_free_fn(void* p) { std::free(p); }
+
+IgpRowSegTable* CpuDevice::row_segs_fn(void* ctx, int32_t slot) { return &static_cast<CpuDevice*>(ctx)->slots_[slot].segs; }
 
 char* CpuDevice::rows_fn(void* ctx, int32_t slot) {
   return reinterpret_cast<char*>(static_cast<CpuDevice*>(ctx)->slots_[slot].rows.data());
@@ -55,6 +71,21 @@ int32_t CpuDevice::submit_fn(void* ctx, int32_t slot, int32_t n, int32_t, int64_
   }
   try {
     s.wf = (wf & IGP_SUBMIT_WANT_FEATURES) != 0;  // (IGP_SUBMIT_NO_UPDATE: nothing to skip here)
+    if (s.segs.nseg > 0) {
+      // in-place rows: gather the table's segments into the slot's rows, as the GPU's dedup insert
+      // reads them into its device copy (row i comes from the last segment starting at or before i)
+      if (s.segs.nseg > IGP_ROW_SEGS) throw std::runtime_error("CpuDevice: segment table count");
+      int32_t at = 0;
+      for (int q = 0; q < s.segs.nseg; ++q) {
+        const IgpRowSeg& g = s.segs.seg[q];
+        if (g.first != at || g.count < 0 || g.count > n - at || !g.src || (g.src & 15))
+          throw std::runtime_error("CpuDevice: segment table does not tile the step's rows");
+        std::memcpy(s.rows.data() + at, reinterpret_cast<const void*>(g.src), size_t(g.count) * sizeof(ReqRec));
+        at += g.count;
+      }
+      if (at != n) throw std::runtime_error("CpuDevice: segment table does not cover the step's rows");
+      d->gathered_.fetch_add(1);
+    }
     d->sc_->score(s.rows.data(), size_t(n), now, true, s.res.data(), s.wf ? s.feat.data() : nullptr);
   } catch (const std::exception& e) {
     set_err(err, errlen, e.what());
@@ -63,7 +94,24 @@ int32_t CpuDevice::submit_fn(void* ctx, int32_t slot, int32_t n, int32_t, int64_
   return 0;
 }
 
-int32_t CpuDevice::wait_fn(void*, int32_t, int64_t, char*, int32_t) { return 0; }  // scored in submit
+// scored in submit; the debug hold makes a step look late (cpu_device.h debug_hold_steps)
+int32_t CpuDevice::wait_fn(void* ctx, int32_t slot, int64_t timeout_us, char*, int32_t) {
+  auto* d = static_cast<CpuDevice*>(ctx);
+  Slot& s = d->slots_[slot];
+  std::unique_lock<std::mutex> l(d->hold_mu_);
+  if (!s.late) {
+    if (d->hold_steps_ <= 0) return 0;
+    --d->hold_steps_;
+    s.late = true;
+    return 1;
+  }
+  if (timeout_us >= 0) return 1;
+  ++d->held_now_;
+  d->hold_cv_.wait(l, [&] { return d->hold_release_; });
+  --d->held_now_;
+  s.late = false;
+  return 0;
+}
 
 const void* CpuDevice::results_fn(void* ctx, int32_t slot) {
   return static_cast<CpuDevice*>(ctx)->slots_[slot].res.data();

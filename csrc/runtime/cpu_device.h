@@ -10,7 +10,9 @@
 //                  CPU tests exercise the exact serving-core paths the GPU ranks run.
 #pragma once
 #include <atomic>
+#include <condition_variable>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -24,7 +26,9 @@ namespace igp {
 
 class CpuDevice {
  public:
-  CpuDevice(std::shared_ptr<CpuScorer> sc, int depth, int cap);
+  // inplace: offer the serving core the in-place row mode (device_ops.h host_alloc / row_segs):
+  // submit gathers the step's rows from the segments its table names
+  CpuDevice(std::shared_ptr<CpuScorer> sc, int depth, int cap, bool inplace = true);
   const IgpDeviceOps* ops() const { return &ops_; }
   // fault injection (tests): after `after` more steps, the next `n` steps fail in submit,
   // scoring nothing
@@ -32,15 +36,42 @@ class CpuDevice {
     pass_steps_.store(after);
     fail_steps_.store(n);
   }
+  // fault injection (tests): the next `n` steps overrun their deadline - wait() answers 1 whatever
+  // its timeout - and the wait without a deadline that follows (the core's quarantine of a late
+  // step) blocks until debug_release_steps(). Such a step was scored; the core must treat its
+  // rows as still being read
+  void debug_hold_steps(int n) {
+    std::lock_guard<std::mutex> g(hold_mu_);
+    hold_steps_ = n;
+    hold_release_ = false;
+  }
+  void debug_release_steps() {
+    {
+      std::lock_guard<std::mutex> g(hold_mu_);
+      hold_steps_ = 0;
+      hold_release_ = true;
+    }
+    hold_cv_.notify_all();
+  }
+  int debug_held_steps() {  // steps blocked in the wait without a deadline right now
+    std::lock_guard<std::mutex> g(hold_mu_);
+    return held_now_;
+  }
+  int64_t gathered_steps() const { return gathered_.load(); }  // steps whose rows came through the table
 
  private:
   struct Slot {
     std::vector<ReqRec> rows;
     std::vector<ResultRec> res;
     std::vector<FeatRec> feat;
+    IgpRowSegTable segs{};
     bool wf = false;
+    bool late = false;  // debug_hold_steps: answered "deadline" once, the next wait blocks
   };
   static char* rows_fn(void* ctx, int32_t slot);
+  static void* host_alloc_fn(void* ctx, uint64_t bytes, uint64_t* dev_addr);
+  static void host_free_fn(void* p);
+  static IgpRowSegTable* row_segs_fn(void* ctx, int32_t slot);
   static int32_t submit_fn(void* ctx, int32_t slot, int32_t n, int32_t seq, int64_t now, int32_t wf, char* err, int32_t errlen);
   static int32_t wait_fn(void* ctx, int32_t slot, int64_t timeout_us, char* err, int32_t errlen);
   static const void* results_fn(void* ctx, int32_t slot);
@@ -48,6 +79,11 @@ class CpuDevice {
   std::shared_ptr<CpuScorer> sc_;
   std::vector<Slot> slots_;
   std::atomic<int> fail_steps_{0}, pass_steps_{0};
+  std::atomic<int64_t> gathered_{0};
+  std::mutex hold_mu_;
+  std::condition_variable hold_cv_;
+  int hold_steps_ = 0, held_now_ = 0;
+  bool hold_release_ = false;
   IgpDeviceOps ops_{};
 };
 

@@ -42,7 +42,9 @@ bool StepClock::all_hold(int64_t gen) const {
 struct ServeCore::Item {
   int kind = 0;                 // 0: a caller thread waits (batch / rows); 1: unary (finisher pool)
   size_t n = 0;
-  std::vector<ReqRec> rows;     // exchange: sorted by owner
+  std::vector<ReqRec> own;      // the rows of an item without a pool buffer
+  ReqRec* rows = nullptr;       // own.data(), or buf->rows (exchange: sorted by owner)
+  RowBuf* buf = nullptr;        // direct ScoreBatch item: its rows sit where the device reads them in place
   std::vector<int32_t> perm;    // exchange: sorted position -> request row (empty: identity)
   std::vector<int32_t> ostart;  // exchange: [world + 1] owner ranges of `rows`
   std::vector<int32_t> ocur;    // next untaken row per owner (direct: [1])
@@ -140,7 +142,12 @@ void ServeCore::resolve_rows(std::vector<wire::TxRow>& rows, Item* it) {
   // FeatureVector already encoded (records.h FV_ENC_BIT; CPU devices ignore the bit)
   const int32_t enc = it->wf ? FV_ENC_BIT : 0;
   it->n = n;
-  it->rows.resize(n);
+  if (it->buf) {
+    it->rows = it->buf->rows;
+  } else {
+    it->own.resize(n);
+    it->rows = it->own.data();
+  }
   thread_local std::vector<std::string_view> ids;
   thread_local std::vector<uint64_t> hs;
   thread_local std::vector<int32_t> slots;
@@ -161,7 +168,7 @@ void ServeCore::resolve_rows(std::vector<wire::TxRow>& rows, Item* it) {
     it->ocur.assign(1, 0);
     it->ostart = {0, int32_t(n)};  // one owner (a world-1 exchange reads the owner ranges too)
     // here, on the ingress threads, not in the stepper: the stepper only combines (issue_step)
-    if (!exchange_) it->mult.build(it->rows.data(), n);
+    if (!exchange_) it->mult.build(it->rows, n);
   } else {
     // counting sort by owner (owner = digest % world, the registry's routing)
     it->ostart.assign(world_ + 1, 0);
@@ -277,7 +284,7 @@ void ServeCore::stream_seg(const Step& st, const Seg& s) {
                                        size_t(s.count));
   it->ser_rows += size_t(s.count);
   record_decisions(r, s.count);
-  audit_seg(r, it->rows.data() + s.item_pos, 0, s.count);
+  audit_seg(r, it->rows + s.item_pos, 0, s.count);
 }
 
 std::string ServeCore::score_batch(const char* data, size_t n, int64_t now, int64_t t0_ns) {
@@ -300,17 +307,21 @@ size_t ServeCore::score_batch_into(const char* data, size_t n, int64_t now, int6
   // 1.79 ms, profiles/r5/host); the item is done with its rows when wait_item returns
   thread_local std::vector<ReqRec> rows_buf;
   thread_local std::vector<uint16_t> mult_buf;  // (the item's sketch counters, likewise)
-  it.rows.swap(rows_buf);
+  it.own.swap(rows_buf);
   it.mult.c.swap(mult_buf);
   struct GiveBack {
     std::vector<ReqRec>& buf;
     std::vector<uint16_t>& mbuf;
     Item& item;
+    ServeCore* core;
     ~GiveBack() {
-      buf.swap(item.rows);
+      buf.swap(item.own);
       mbuf.swap(item.mult.c);
+      // the item's own reference only: a step that still reads the buffer (late, or failed and
+      // not yet disposed of) keeps it out of the pool (release_step_ref)
+      if (item.buf) core->release_rowbuf(item.buf);
     }
-  } give_back{rows_buf, mult_buf, it};
+  } give_back{rows_buf, mult_buf, it, this};
   it.kind = 0;
   it.now = now >= 0 ? now : wall_s();
   it.wf = opt_.features;
@@ -321,6 +332,9 @@ size_t ServeCore::score_batch_into(const char* data, size_t n, int64_t now, int6
   wire::parse_batch_rows(data, n, rows);
   const int64_t tb = now_ns();
   if (rows.empty()) return 0;
+  // a device that reads rows in place: the rows are resolved straight into a pinned buffer of
+  // the core's pool, and the stepper copies nothing (issue_step)
+  if (!exchange_) it.buf = acquire_rowbuf(rows.size());
   resolve_rows(rows, &it);
   const int64_t tc = now_ns();
   char* const out = alloc(it.n * wire::kMaxBatchRowBytes);
@@ -374,10 +388,11 @@ void ServeCore::score_rows(const ReqRec* rows, const int32_t* owners, size_t n, 
   it.res = res;
   it.feat = it.wf ? feat : nullptr;
   if (world_ == 1) {
-    it.rows.assign(rows, rows + n);
+    it.own.assign(rows, rows + n);
+    it.rows = it.own.data();
     it.ocur.assign(1, 0);
     it.ostart = {0, int32_t(n)};
-    if (!exchange_) it.mult.build(it.rows.data(), n);
+    if (!exchange_) it.mult.build(it.rows, n);
   } else {
     if (!owners) throw std::runtime_error("ServeCore.score_rows: owners required when world > 1");
     it.ostart.assign(world_ + 1, 0);
@@ -389,7 +404,8 @@ void ServeCore::score_rows(const ReqRec* rows, const int32_t* owners, size_t n, 
     it.ocur.assign(it.ostart.begin(), it.ostart.end() - 1);
     std::vector<int32_t> fill(it.ocur);
     it.perm.resize(n);
-    it.rows.resize(n);
+    it.own.resize(n);
+    it.rows = it.own.data();
     for (size_t k = 0; k < n; ++k) {
       const int32_t pos = fill[owners[k]]++;
       it.perm[pos] = int32_t(k);
@@ -469,7 +485,8 @@ void ServeCore::submit_tx_many(const TxCall* calls, size_t n, int64_t now) {
       it->res = &it->res1;
       it->feat = it->wf ? &it->feat1 : nullptr;
       it->n = 1;
-      it->rows.resize(1);
+      it->own.resize(1);
+      it->rows = it->own.data();
       it->rows[0] = rows[k].rec;
       it->rows[0].slot = slots[m++];
       it->rows[0].tx_type |= enc;
@@ -677,10 +694,33 @@ bool ServeCore::issue_step(std::unique_lock<std::mutex>& lk, bool allow_empty) {
   // pack the rows into the slot's pinned buffer (outside the queue lock)
   const int64_t t0 = now_ns();
   char* buf = dev_->rows(dev_->ctx, slot);
+  bool inplace = false;
   if (!exchange_) {
-    for (const Seg& s : st->segs)
-      std::memcpy(buf + size_t(s.dev_pos) * sizeof(ReqRec), s.item->rows.data() + s.item_pos,
-                  size_t(s.count) * sizeof(ReqRec));
+    // In place: every segment lies in a pool buffer of the current device, and the table holds
+    // them all. The stepper then writes the table and touches no row; the step takes a reference
+    // on each buffer, dropped when the step is released (release_step_ref) and not before: the
+    // device reads them during the copy stage, whatever becomes of the items meanwhile.
+    IgpRowSegTable* tab = dev_->row_segs ? dev_->row_segs(dev_->ctx, slot) : nullptr;
+    inplace = tab && n > 0 && st->segs.size() <= size_t(IGP_ROW_SEGS);
+    if (inplace) {
+      const int64_t gen = pool_gen_now_.load(std::memory_order_relaxed);
+      for (const Seg& s : st->segs) inplace = inplace && s.item->buf && s.item->buf->gen == gen;
+    }
+    if (inplace) {
+      int k = 0;
+      for (const Seg& s : st->segs) {
+        RowBuf* b = s.item->buf;
+        b->refs.fetch_add(1, std::memory_order_relaxed);
+        st->bufs.push_back(b);
+        tab->seg[k++] = IgpRowSeg{b->dev + uint64_t(s.item_pos) * sizeof(ReqRec), s.dev_pos, s.count};
+      }
+      tab->nseg = k;
+    } else {
+      if (tab) tab->nseg = 0;
+      for (const Seg& s : st->segs)
+        std::memcpy(buf + size_t(s.dev_pos) * sizeof(ReqRec), s.item->rows + s.item_pos,
+                    size_t(s.count) * sizeof(ReqRec));
+    }
   } else {
     ReqRec* chunks = reinterpret_cast<ReqRec*>(buf);
     const size_t stride = size_t(cap_) + 1;
@@ -691,7 +731,7 @@ bool ServeCore::issue_step(std::unique_lock<std::mutex>& lk, bool allow_empty) {
       h.ts = now;        // this sender's clock: the owner scores the step at its senders' latest
     }
     for (const Seg& s : st->segs)
-      std::memcpy(chunks + size_t(s.owner) * stride + 1 + s.dev_pos, s.item->rows.data() + s.item_pos,
+      std::memcpy(chunks + size_t(s.owner) * stride + 1 + s.dev_pos, s.item->rows + s.item_pos,
                   size_t(s.count) * sizeof(ReqRec));
   }
   // can an account have more rows in this step than the device's K1 applies by itself? The
@@ -724,6 +764,8 @@ bool ServeCore::issue_step(std::unique_lock<std::mutex>& lk, bool allow_empty) {
     st_.submit_ns += t2 - t1;
     st_.steps += 1;
     if (n == 0) st_.empty_steps += 1;
+    else if (inplace) st_.inplace_steps += 1;
+    else if (!exchange_) st_.packed_steps += 1;
     st_.max_step_rows = std::max<int64_t>(st_.max_step_rows, n);
     for (const Seg& s : st->segs) {
       if (s.item->kind == 1) st_.unary += 1;
@@ -892,7 +934,7 @@ void ServeCore::finish_seg(const Step& st, const Seg& s) {
       if (f) std::memcpy(it->feat + s.item_pos, f + s.dev_pos, size_t(s.count) * kFeatBytes);
     }
     record_decisions(r, s.count);
-    audit_seg(r, it->rows.data() + s.item_pos, 0, s.count);
+    audit_seg(r, it->rows + s.item_pos, 0, s.count);
     return;
   }
   const size_t W = kResBytes + (st.wf ? kFeatBytes : 0);
@@ -907,7 +949,7 @@ void ServeCore::finish_seg(const Step& st, const Seg& s) {
     if (it->feat && f) it->feat[dst] = f[i];
   }
   record_decisions(r, s.count);
-  audit_seg(r, it->rows.data() + s.item_pos, s.owner, s.count);
+  audit_seg(r, it->rows + s.item_pos, s.owner, s.count);
 }
 
 void ServeCore::audit_seg(const ResultRec* r, const ReqRec* rows, int owner, int n) {
@@ -945,6 +987,10 @@ void ServeCore::release_step_ref(Step* st) {
     st_.release_ns += now_ns() - st->t_done;
   }
   st->t_done = 0;
+  // the step is done with the request buffers it read in place (before the slot, and with it
+  // this Step object, goes back to the stepper)
+  for (RowBuf* b : st->bufs) release_rowbuf(b);
+  st->bufs.clear();
   {
     std::lock_guard<std::mutex> lk(q_mu_);
     free_slots_.push_back(st->slot);
@@ -1031,7 +1077,10 @@ void ServeCore::set_device(const IgpDeviceOps* dev) {
   if (!dev || dev->abi != IGP_DEVICE_OPS_ABI) throw std::runtime_error("ServeCore.set_device: ABI mismatch");
   if (dev->world != world_ || (dev->exchange != 0) != exchange_)
     throw std::runtime_error("ServeCore.set_device: the new device must have the same world / mode");
-  dev_ = dev;
+  // row buffers come from the device that reads them: the pool starts over. Requests that hold
+  // a buffer of the old device right now (parsing, not yet queued) are packed, and their buffers
+  // are freed, not pooled, when they return
+  close_pool(dev);
   cap_ = dev->cap;
   depth_ = dev->depth;
   steps_.clear();
@@ -1107,6 +1156,82 @@ void ServeCore::stop() {
   l_cv_.notify_all();
   for (size_t i = 2; i < threads_.size(); ++i) threads_[i].join();
   threads_.clear();
+  close_pool(nullptr);  // every step was released: only requests still returning hold a buffer
+}
+
+// ---------------------------------------------------------------------------- row buffers
+// A buffer for n rows: the one this thread used last when it is free (its lines are in this
+// core's cache, and nobody else read them since: the stepper does not touch in-place rows), else
+// the most recently returned. A buffer too small is replaced (free + alloc), so each grows to the
+// largest request it has carried.
+ServeCore::RowBuf* ServeCore::acquire_rowbuf(size_t n) {
+  const IgpDeviceOps* dev;
+  RowBuf* b = nullptr;
+  int64_t gen;
+  thread_local const RowBuf* last = nullptr;  // compared, never dereferenced
+  {
+    std::lock_guard<std::mutex> g(pool_mu_);
+    dev = dev_;
+    if (pool_closed_ || !dev->host_alloc || !dev->host_free || !dev->row_segs) return nullptr;
+    gen = pool_gen_;
+    if (!pool_.empty()) {
+      auto pos = std::find(pool_.begin(), pool_.end(), last);
+      if (pos == pool_.end()) pos = pool_.end() - 1;
+      b = *pos;
+      pool_.erase(pos);
+    }
+    if (b && b->cap < n) {
+      drop_rowbuf(b);
+      b = nullptr;
+    }
+    if (!b) ++pool_live_;  // (allocated below, outside the lock)
+  }
+  if (!b) {
+    // whole 64-row blocks: requests of slightly different sizes share a buffer
+    const size_t cap = (n + 63) & ~size_t(63);
+    uint64_t da = 0;
+    void* p = dev->host_alloc(dev->ctx, uint64_t(cap) * sizeof(ReqRec), &da);
+    if (!p || (reinterpret_cast<uintptr_t>(p) & 15) || (da & 15)) {
+      if (p) dev->host_free(p);
+      std::lock_guard<std::mutex> g(pool_mu_);
+      --pool_live_;
+      return nullptr;  // the item keeps its rows itself and its steps are packed
+    }
+    b = new RowBuf();
+    b->rows = static_cast<ReqRec*>(p);
+    b->dev = da;
+    b->cap = cap;
+    b->gen = gen;
+    b->free_fn = dev->host_free;
+  }
+  b->refs.store(1, std::memory_order_relaxed);
+  last = b;
+  return b;
+}
+
+void ServeCore::drop_rowbuf(RowBuf* b) {
+  b->free_fn(b->rows);
+  delete b;
+  --pool_live_;
+}
+
+void ServeCore::release_rowbuf(RowBuf* b) {
+  if (b->refs.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
+  std::lock_guard<std::mutex> g(pool_mu_);
+  if (pool_closed_ || b->gen != pool_gen_) drop_rowbuf(b);
+  else pool_.push_back(b);
+}
+
+// Free the pooled buffers and start a new generation: for the device `next` (set_device; dev_
+// changes under the pool's lock, where acquire_rowbuf reads it), or for none (stop: no buffer is
+// handed out any more)
+void ServeCore::close_pool(const IgpDeviceOps* next) {
+  std::lock_guard<std::mutex> g(pool_mu_);
+  for (RowBuf* b : pool_) drop_rowbuf(b);
+  pool_.clear();
+  pool_gen_now_.store(++pool_gen_, std::memory_order_relaxed);
+  if (next) dev_ = next;
+  else pool_closed_ = true;
 }
 
 ServeStats ServeCore::stats(bool reset) {
@@ -1128,6 +1253,11 @@ ServeStats ServeCore::stats(bool reset) {
   s.ml_high = hi_.load();
   s.blacklisted = bl_.load();
   s.scored = scored_.load();
+  {
+    std::lock_guard<std::mutex> g(pool_mu_);
+    s.rowbufs = pool_live_;
+    s.rowbufs_free = int64_t(pool_.size());
+  }
   return s;
 }
 

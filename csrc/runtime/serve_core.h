@@ -7,7 +7,13 @@
 //   stepper thread
 //     forms device micro-batches from the FIFO of items (up to the pipeline's capacity, or
 //     per-owner chunk capacity in exchange mode), packs the rows into the slot's pinned
-//     buffer, launches the slot through the device function table (device_ops.h)
+//     buffer, launches the slot through the device function table (device_ops.h).
+//     A direct device that offers it (device_ops.h host_alloc / row_segs) reads ScoreBatch rows
+//     in place: the ingress thread resolves them into a pinned buffer from the core's pool, and
+//     the stepper only writes the slot's segment table. A step holds a reference on every
+//     buffer it names until it is released, so a late or failed step never reads rows of a
+//     later request. Steps with unary calls, score_rows items or more than IGP_ROW_SEGS
+//     segments are packed
 //   completion thread
 //     waits for slots in submit order; unary items are finished (copy + serialise) by a
 //     finisher pool and handed back through a completion queue polled from Python
@@ -102,6 +108,11 @@ struct ServeStats {
   // slot is free again), and the stepper's waits with rows queued: for the next slot (in-order
   // slots of the exchange) or for more rows (a step is formed at 7/8 full or after max_wait)
   int64_t release_ns = 0, slot_wait_ns = 0, rows_wait_ns = 0, slot_waits = 0, slot_wait_inflight = 0;
+  // direct mode: steps whose rows the device read in place (a segment table, nothing copied) and
+  // steps packed into the slot's request buffer (empty steps count as neither)
+  int64_t inplace_steps = 0, packed_steps = 0;
+  // request row buffers from the device (not reset): allocated now, and of those in the pool
+  int64_t rowbufs = 0, rowbufs_free = 0;
   // cumulative decision counters (never reset)
   int64_t actions[4] = {0, 0, 0, 0};
   int64_t deciles[11] = {0};
@@ -215,6 +226,21 @@ class ServeCore {
     int32_t dev_pos;     // direct: first row in the slot; exchange: first index in the owner's chunk
     int32_t count;
   };
+  // One request's rows in host memory the device reads in place (device_ops.h host_alloc).
+  // refs: the item that fills it + every step whose segment table names it; back to the pool
+  // (or, once the pool moved on to another device or closed, freed) at zero
+  struct RowBuf {
+    ReqRec* rows = nullptr;
+    uint64_t dev = 0;       // the address the device reads `rows` at
+    size_t cap = 0;         // rows
+    int64_t gen = 0;        // pool generation (set_device starts a new one)
+    void (*free_fn)(void*) = nullptr;
+    std::atomic<int> refs{0};
+  };
+  RowBuf* acquire_rowbuf(size_t n);   // null: the device has no in-place mode (or cannot allocate)
+  void release_rowbuf(RowBuf* b);
+  void drop_rowbuf(RowBuf* b);        // pool_mu_ held
+  void close_pool(const IgpDeviceOps* next);
   struct Step {
     int slot = 0;
     int32_t seq = 0;
@@ -222,6 +248,7 @@ class ServeCore {
     bool wf = false;
     int64_t t_submit = 0, t_done = 0;
     std::vector<Seg> segs;
+    std::vector<RowBuf*> bufs;  // in-place step: one reference per segment's buffer
     std::atomic<int> refs{0};
     bool failed = false;
     std::string err;
@@ -304,6 +331,13 @@ class ServeCore {
   static constexpr size_t kLinkQueue = 4;
   std::deque<std::pair<std::vector<uint64_t>, std::vector<int64_t>>> lq_;
   bool l_stop_ = false;
+
+  // request row buffers (pool_mu_): free ones, most recently returned last
+  std::mutex pool_mu_;
+  std::vector<RowBuf*> pool_;
+  int64_t pool_gen_ = 0, pool_live_ = 0;
+  std::atomic<int64_t> pool_gen_now_{0};  // pool_gen_ for the stepper (no lock per step)
+  bool pool_closed_ = false;
 
   std::atomic<int64_t> issued_{0};
   std::atomic<int> late_{0};

@@ -146,6 +146,10 @@ class GPUConfig:
     native_serving: bool = True
     serve_depth: int = 6          # pipeline slots (batches in flight) of a shard's device (<= 7; profiles/r6/ad)
     unary_depth: int = 4          # steps in flight while unary calls are arriving (ServeCore Options.unary_depth)
+    # ScoreBatch rows are read by the device where the ingress threads wrote them (pinned request
+    # buffers of the serving core + a segment table per step) instead of being packed into the
+    # slot's slab by the stepper; off: every step is packed
+    inplace_rows: bool = True
     serve_finishers: int = 2      # unary response threads
     exchange_timeout_s: float = 10.0  # multi-rank step deadline: a peer that misses it failed
     # native account RPCs (csrc/runtime/acct_core.cpp, engine/acct.py): PredictLTV,

@@ -692,10 +692,13 @@ class NativeCpuBackend:
 
     core = None
 
-    def native_device(self, depth: int = 2, cap: int = 8192):
-        """A CpuDevice over this shard's CpuScorer for the serving core."""
+    def native_device(self, depth: int = 2, cap: int = 8192, inplace: Optional[bool] = None):
+        """A CpuDevice over this shard's CpuScorer for the serving core. ``inplace`` (default
+        ``cfg.gpu.inplace_rows``): the core's ScoreBatch rows are read where the ingress threads
+        resolved them (a segment table per step) instead of being packed by the stepper."""
         from ..native import native
-        self._device = native().CpuDevice(self.sc, int(depth), int(cap))
+        inplace = bool(self.cfg.gpu.inplace_rows) if inplace is None else bool(inplace)
+        self._device = native().CpuDevice(self.sc, int(depth), int(cap), inplace)
         return self._device
 
     def attach_core(self, core) -> None:

@@ -127,7 +127,15 @@ class GpuScorer:
         B = self.bmax
         self.slab_bytes = HDR_BYTES + REQ_BYTES * B
         self.depth = int(pipeline_depth)
-        self.host_slab = [torch.zeros(self.slab_bytes, dtype=torch.uint8).pin_memory() for _ in range(self.depth)]
+        # the pinned slab of a slot: [BatchHdr | ReqRec x B | segment table]. The table (device_ops.h
+        # IgpRowSegTable, 16-byte aligned behind the rows) is the serving core's: with a live count
+        # in it the dedup insert reads the step's rows from the requests' own pinned buffers
+        # instead of the slab (cfg.gpu.inplace_rows); zero, as every other submitter leaves it,
+        # means the rows are in the slab
+        self.inplace_rows = bool(getattr(cfg.gpu, "inplace_rows", True))
+        host_bytes = self.slab_bytes + K.ROW_SEG_TABLE_BYTES
+        self.host_slab = [torch.zeros(host_bytes, dtype=torch.uint8).pin_memory() for _ in range(self.depth)]
+        self.host_segs = [t[self.slab_bytes:] for t in self.host_slab]
         self.host_slab_np = [t.numpy() for t in self.host_slab]
         self.host_res = [torch.zeros((B, 2), dtype=torch.int32).pin_memory() for _ in range(self.depth)]
         self.host_feat = [torch.zeros((B, 32), dtype=torch.int32).pin_memory() for _ in range(self.depth)]
@@ -272,7 +280,8 @@ class GpuScorer:
             # the dedup insert reads the batch from the pinned slab and writes the device copy (an
             # H2D copy first and the insert from HBM: same engine_only / serving, round-5 A/B
             # profiles/r5/eng/dedup_src)
-            K.dedup_insert(self.store, self.cfg_dev, sb.req, bucket, sb.hdr, src=self.host_slab[slot])
+            K.dedup_insert(self.store, self.cfg_dev, sb.req, bucket, sb.hdr, src=self.host_slab[slot],
+                           segs=self.host_segs[slot])
             return
         K.memcpy_async(sb.dev_slab, self.host_slab[slot], HDR_BYTES + REQ_BYTES * bucket)
 
@@ -356,6 +365,8 @@ class GpuScorer:
                                     self.depth, [t.data_ptr() for t in self.host_slab])
             for slot in range(self.depth):  # what the native serving core reads after a wait
                 d.set_host_results(slot, self.host_res[slot].data_ptr(), self.host_feat[slot].data_ptr())
+                if self.inplace_rows and self.update_features:  # (the plain H2D copy stage reads the slab only)
+                    d.set_row_segs(slot, self.host_segs[slot].data_ptr())
             if self.state_clock is not None:
                 d.set_state_clock(self.state_clock)
             for (b, slot), g in self.graphs.items():

@@ -164,6 +164,10 @@ def feature_assemble(store, hdr: torch.Tensor, cfg_dev: torch.Tensor, req: torch
 
 
 # --------------------------------------------------------------------------- K6
+ROW_SEGS = 16                               # device_ops.h IGP_ROW_SEGS
+ROW_SEG_TABLE_BYTES = 16 + 16 * ROW_SEGS    # IgpRowSegTable: {nseg, pad x 3} + {src u64, first, count} x ROW_SEGS
+
+
 def update_args(store, cfg_dev: torch.Tensor, req: torch.Tensor, n_max: int, n: int = 0,
                 hdr: Optional[torch.Tensor] = None, region: int = DEDUP_STANDALONE) -> dict:
     dev = store.device
@@ -196,17 +200,24 @@ def feature_update(store, cfg_dev: torch.Tensor, req: torch.Tensor, n_max: int, 
 
 
 def dedup_insert(store, cfg_dev: torch.Tensor, req: torch.Tensor, n_max: int, hdr: torch.Tensor,
-                 src: Optional[torch.Tensor] = None, xsrc: Optional[dict] = None) -> None:
+                 src: Optional[torch.Tensor] = None, xsrc: Optional[dict] = None,
+                 segs: Optional[torch.Tensor] = None) -> None:
     """Scorer head: register the batch's accounts in its dedup region (before K1), with the
     per-account row lists and the multi-event account list :func:`update_segments` reads.
     ``src``: the pinned host slab [BatchHdr | ReqRec x n_max] - the kernel reads the batch from
-    it and writes ``hdr`` / ``req`` itself (no H2D copy before it). ``xsrc``: the rows-region
+    it and writes ``hdr`` / ``req`` itself (no H2D copy before it). ``segs`` (with ``src``): the
+    slot's pinned segment table (:data:`ROW_SEG_TABLE_BYTES`; device_ops.h IgpRowSegTable) - with a
+    live count in it the rows come from the host buffers it names, not from the slab. ``xsrc``: the rows-region
     exchange - dict(recv=host address of sender 0's chunk for this owner, pstride=records between
     senders, N=senders, C=chunk capacity, route=int32 [n_max + 1], hdr=host address of the batch
     header): the kernel compacts the chunks into ``req`` itself (launch.h UpdateArgs)."""
     d = update_args(store, cfg_dev, req, n_max, hdr=hdr, region=-1)
     if src is not None:
         d["src"] = _host_or_dev(src, "src", 16 + 48 * n_max, store.device, torch.uint8)
+    if segs is not None:
+        if src is None or segs.is_cuda:
+            raise ValueError("dedup_insert: a segment table is pinned host memory and goes with a slab source")
+        d["segs"] = _host_or_dev(segs, "segs", ROW_SEG_TABLE_BYTES, store.device, torch.uint8)
     if xsrc is not None:
         d.update(xrecv=int(xsrc["recv"]), xpstride=int(xsrc["pstride"]), xn=int(xsrc["N"]), xc=int(xsrc["C"]),
                  route=_need(xsrc["route"], "route", torch.int32, n_max + 1, store.device), xhdr=int(xsrc["hdr"]))
