@@ -400,6 +400,53 @@ PYBIND11_MODULE(_hipk, m) {
       throw std::runtime_error("quant_rows: scale > 0, off 0 | 128, zero point inside the type");
     launch_or_record([a](hipStream_t st) { launch_quant_rows(a, st); }, s, "quant_rows");
   });
+  m.attr("SVM_MAX_F") = SVM_MAX_F;
+  m.attr("SVM_MAX_DEGREE") = SVM_MAX_DEGREE;
+  m.def("svm_tile", [](int M) { return svm_tile(M); });
+  m.def("svm", [](py::dict d, uintptr_t s) {
+    auto getf = [&d](const char* k, float def) { return d.contains(k) ? d[k].cast<float>() : def; };
+    SvmArgs a{};
+    a.X = ptr<const float*>(d, "X");
+    a.sv = ptr<const float*>(d, "sv");
+    a.coef = ptr<const float*>(d, "coef");
+    a.sv_norm = ptr<const float*>(d, "sv_norm");
+    a.in_scale = ptr<const float*>(d, "in_scale");
+    a.in_shift = ptr<const float*>(d, "in_shift");
+    a.Y = ptr<float*>(d, "Y");
+    a.m_ptr = ptr<const int32_t*>(d, "m_ptr");
+    a.M = geti(d, "M");
+    a.F = geti(d, "F");
+    a.S = geti(d, "S");
+    a.ldx = geti(d, "ldx");
+    a.ldy = geti(d, "ldy");
+    a.f_pad = geti(d, "f_pad");
+    a.kernel = geti(d, "kernel");
+    a.degree = geti(d, "degree");
+    a.gamma = getf("gamma", 0.f);
+    a.coef0 = getf("coef0", 0.f);
+    a.rho = getf("rho", 0.f);
+    a.platt = geti(d, "platt");
+    a.prob_a = getf("prob_a", 0.f);
+    a.prob_b = getf("prob_b", 0.f);
+    a.one_class = geti(d, "one_class");
+    a.post_scale = getf("post_scale", 1.f);
+    a.post_shift = getf("post_shift", 0.f);
+    a.act = geti(d, "act");
+    a.tile = geti(d, "tile");
+    const int sv_rows = geti(d, "sv_rows");
+    if (!a.X || !a.sv || !a.coef || !a.in_scale || !a.in_shift || !a.Y) throw std::runtime_error("svm: missing pointers");
+    if (a.M < 0 || a.F < 1 || a.F > SVM_MAX_F || a.S < 1 || a.ldx < a.F || a.ldy < 1)
+      throw std::runtime_error("svm: sizes (1 <= F <= 256, S >= 1, ldx >= F, ldy >= 1)");
+    if (a.f_pad % SVM_TILE_K || a.f_pad < a.F || a.f_pad > SVM_MAX_F || sv_rows % SVM_TILE_S || sv_rows < a.S)
+      throw std::runtime_error("svm: the support vector table must be padded to [S_pad % 64 == 0][f_pad % 32 == 0]");
+    if ((reinterpret_cast<uintptr_t>(a.sv) & 15)) throw std::runtime_error("svm: the support vector table must be 16-byte aligned");
+    if (a.kernel < SVM_LINEAR || a.kernel > SVM_SIGMOID) throw std::runtime_error("svm: kernel type");
+    if (a.kernel == SVM_RBF && !a.sv_norm) throw std::runtime_error("svm: an RBF kernel needs sv_norm");
+    if (a.kernel == SVM_POLY && (a.degree < 0 || a.degree > SVM_MAX_DEGREE)) throw std::runtime_error("svm: POLY degree in [0, 16]");
+    if (a.platt < 0 || a.platt > 2 || (a.act != 0 && a.act != 2)) throw std::runtime_error("svm: platt 0 | 1 | 2, act none | sigmoid");
+    if (a.tile != 0 && a.tile != 16 && a.tile != 32 && a.tile != 64) throw std::runtime_error("svm: tile 0 | 16 | 32 | 64");
+    launch_or_record([a](hipStream_t st) { launch_svm(a, st); }, s, "svm");
+  });
   m.def("join", [](py::dict d, uintptr_t s) {
     JoinArgs a{};
     a.A = ptr<const void*>(d, "A");

@@ -250,6 +250,39 @@ struct QuantRowsArgs {
 };
 void launch_quant_rows(const QuantRowsArgs& a, hipStream_t st);
 
+// ---- kernel machines (svm.hip): ai.onnx.ml SVMRegressor / two-class SVMClassifier,
+//   dec[m] = sum_i coef[i] * K(x'_m, sv_i) + rho,  x' = x * in_scale + in_shift,  d = x' . sv_i
+// on v_mfma_f32_16x16x4_f32, f32 throughout. The epilogue: Platt 1 / (1 + exp(a dec + b)) (flipped
+// to 1 - p), else the one-class sign; then v * post_scale + post_shift, then the activation.
+enum SvmKernel : int32_t { SVM_LINEAR = 0, SVM_POLY = 1, SVM_RBF = 2, SVM_SIGMOID = 3 };
+constexpr int SVM_MAX_F = 256;    // widest input the kernel stages (its X tile lives in LDS)
+constexpr int SVM_MAX_DEGREE = 16;
+constexpr int SVM_TILE_S = 64;    // support vectors per streamed tile (the table is padded to it)
+constexpr int SVM_TILE_K = 32;    // columns per streamed chunk (the table is padded to it)
+struct SvmArgs {
+  const float* X;           // [M][ldx] f32
+  const float* sv;          // [S_pad(64)][f_pad = round_up(F, 32)] zero padded (RBF: centred)
+  const float* coef;        // [S_pad]
+  const float* sv_norm;     // [S_pad] |sv_i|^2 (RBF; nullable otherwise)
+  const float* in_scale;    // [f_pad] input affine (ones / zeros when the model has none)
+  const float* in_shift;    // [f_pad]
+  float* Y;                 // [M][ldy], column 0
+  const int32_t* m_ptr;     // live rows in device memory (nullable -> M)
+  int32_t M, F, S;
+  int32_t ldx, ldy, f_pad;
+  int32_t kernel;           // SvmKernel
+  int32_t degree;           // POLY: 0 .. SVM_MAX_DEGREE
+  float gamma, coef0, rho;
+  int32_t platt;            // 0 none, 1 p = 1 / (1 + exp(a dec + b)), 2 the other class: 1 - p
+  float prob_a, prob_b;
+  int32_t one_class;        // dec > 0 ? 1 : -1
+  float post_scale, post_shift;
+  int32_t act;              // 0 none, 2 sigmoid (GemmArgs::act codes)
+  int32_t tile;             // rows per workgroup: 0 -> svm_tile(M), else 16 | 32 | 64
+};
+void launch_svm(const SvmArgs& a, hipStream_t st);
+int svm_tile(int M);  // rows per workgroup launch_svm picks (16 | 32 | 64)
+
 // DAG join of two branches (join.hip): op 0 Y = A + B (na columns), op 1 Y = [A | B]
 struct JoinArgs {
   const void* A;

@@ -281,7 +281,30 @@ PYBIND11_MODULE(_native, m) {
         d["max_feature"] = e->max_feature;
         d["classlabels"] = vec_np(e->classlabels);
         return d;
-      }, py::arg("node_index"), py::arg("limit") = 12);
+      }, py::arg("node_index"), py::arg("limit") = 12)
+      // the compiled form of an SVMClassifier / SVMRegressor node (csrc/runtime/svm.h)
+      .def("svm_info", [](const exec::Executor& ex, size_t node_index) {
+        const svm::SvmModel* m = ex.svm_model(node_index);
+        if (!m) throw std::runtime_error("node is not an SVMClassifier / SVMRegressor");
+        py::dict d;
+        d["classifier"] = m->classifier;
+        d["kernel"] = m->kernel;
+        d["gamma"] = m->gamma;
+        d["coef0"] = m->coef0;
+        d["degree"] = m->degree;
+        d["n_sv"] = m->n_sv;
+        d["n_feat"] = m->n_feat;
+        d["sv"] = py::array_t<float>({m->n_sv, m->n_feat}, m->sv.data());
+        d["coef"] = vec_np(m->coef);
+        d["rho"] = m->rho;
+        d["post"] = m->post;
+        d["one_class"] = m->one_class;
+        d["platt"] = m->platt;
+        d["prob_a"] = m->prob_a;
+        d["prob_b"] = m->prob_b;
+        d["classlabels"] = vec_np(m->classlabels);
+        return d;
+      }, py::arg("node_index"));
 
   py::class_<wire::RequestBatch, std::shared_ptr<wire::RequestBatch>>(m, "RequestBatch")
       .def(py::init<>())

@@ -548,7 +548,14 @@ Executor::Executor(onnx::Model model) : model_(std::move(model)) {
     const auto& op = g.nodes[k].op_type;
     if (op == "TreeEnsembleClassifier" || op == "TreeEnsembleRegressor" || op == "TreeEnsemble")
       ensembles_[k] = std::make_shared<trees::Ensemble>(trees::compile(g.nodes[k]));
+    else if (op == "SVMClassifier" || op == "SVMRegressor")
+      svms_[k] = std::make_shared<svm::SvmModel>(svm::compile(g.nodes[k]));
   }
+}
+
+const svm::SvmModel* Executor::svm_model(size_t node_index) const {
+  auto it = svms_.find(node_index);
+  return it == svms_.end() ? nullptr : it->second.get();
 }
 
 const trees::Ensemble* Executor::ensemble(size_t node_index) const {
@@ -784,6 +791,42 @@ std::map<std::string, Tensor> Executor::run(const std::map<std::string, Tensor>&
       vals[n.outputs[0]] = std::move(labels);
       if (n.outputs.size() > 1) vals[n.outputs[1]] = std::move(scores);
       continue;
+    } else if (op == "SVMClassifier" || op == "SVMRegressor") {
+      const svm::SvmModel& m = *svm_model(k);
+      const Tensor& x = get(n.inputs[0]);
+      const auto xf = as_float(x);
+      const int64_t C = x.dims.empty() ? 1 : x.dims.back();
+      const int64_t N = x.dims.size() <= 1 ? 1 : x.numel() / std::max<int64_t>(C, 1);
+      std::vector<float> dec(size_t(N), 0.f);
+      svm::decision(m, xf.data(), N, C, dec.data());
+      if (!m.classifier) {
+        out = make({N, 1});
+        for (int64_t i = 0; i < N; ++i) {
+          out.f[i] = m.one_class ? (dec[i] > 0.f ? 1.f : -1.f) : dec[i];
+          post_row(m.post, &out.f[i], 1);
+        }
+      } else {
+        // outputs as LinearClassifier writes them: label [N] int64, scores [N][2]
+        Tensor labels = make({N}, INT64), scores = make({N, 2});
+        for (int64_t i = 0; i < N; ++i) {
+          float* z = &scores.f[i * 2];
+          int64_t best;
+          if (m.platt) {
+            z[0] = 1.f / (1.f + std::exp(m.prob_a * dec[i] + m.prob_b));
+            z[1] = 1.f - z[0];
+            best = z[1] > z[0] ? 1 : 0;
+          } else {
+            z[0] = dec[i];
+            z[1] = -dec[i];
+            best = dec[i] > 0.f ? 0 : 1;
+            post_row(m.post, z, 2);
+          }
+          labels.i[i] = m.classlabels[best];
+        }
+        vals[n.outputs[0]] = std::move(labels);
+        if (n.outputs.size() > 1) vals[n.outputs[1]] = std::move(scores);
+        continue;
+      }
     } else if (op == "LinearRegressor") {
       const Tensor& x = get(n.inputs[0]);
       const int64_t E = n.geti("targets", 1);

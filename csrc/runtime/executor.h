@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "onnx_model.h"
+#include "svm.h"
 #include "trees.h"
 
 namespace igp::exec {
@@ -25,10 +26,13 @@ class Executor {
   const onnx::Model& model() const { return model_; }
   // compiled tree ensembles by node index (shared with the device plan compiler)
   const trees::Ensemble* ensemble(size_t node_index) const;
+  // compiled SVMClassifier / SVMRegressor nodes by node index (shared with the plan compiler too)
+  const svm::SvmModel* svm_model(size_t node_index) const;
 
  private:
   onnx::Model model_;
   std::map<size_t, std::shared_ptr<trees::Ensemble>> ensembles_;
+  std::map<size_t, std::shared_ptr<svm::SvmModel>> svms_;
   std::vector<size_t> order_;  // topological node order
 };
 

@@ -251,6 +251,8 @@ class DeviceModel:
                 K.dense(cur, s.w, s.b, out, bucket, s.n, s.k, act=s.act, m_ptr=m_ptr)
             elif s.kind == "qdense":  # int8 MFMA on the quantised bytes of the producing step
                 K.qdense(cur, s.w8, s.corr, s.mult, s.b, out, bucket, s.n, s.k, act=s.act, out_q=s.out_q, m_ptr=m_ptr)
+            elif s.kind == "svm":  # kernel machine on the f32 matrix cores, whatever the plan's precision
+                K.svm(s, cur, out, bucket, m_ptr=m_ptr)
             elif s.kind == "quant":
                 K.quantize(cur, out, bucket, s.width, s.scale, s.zp, s.qtype, m_ptr=m_ptr)
             elif s.kind == "dequant":

@@ -118,7 +118,12 @@ def plan_importance(plan, width: int) -> Dict[str, float]:
             score += np.bincount(feat.astype(np.int64), minlength=width)[:width]
     else:
         first = next((s for s in plan.steps if s.kind in ("dense", "qdense", "head")), None)
-        if first is not None:
+        if plan.steps and plan.steps[0].kind == "svm":
+            # a kernel machine: the weight vector of its linear part, |sum_i coef_i sv_i| per column
+            sv = plan.steps[0]
+            w = np.abs(sv.coef_np.astype(np.float64) @ sv.sv_np.astype(np.float64))
+            score[:min(width, w.size)] = w[:width]
+        elif first is not None:
             w = first.w1_np if first.kind == "head" else first.w_np   # [N, K]
             score[:min(width, w.shape[1])] = np.abs(w).sum(axis=0)[:width]
     tot = score.sum()

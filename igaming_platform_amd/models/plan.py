@@ -44,6 +44,14 @@ steps:
   ``w_q - z_w`` must fit int8; K <= 32768 (the int32 accumulator bound). The QOperator format
   (QLinearMatMul ...), MatMulInteger / DynamicQuantizeLinear, ``block_size``, 4-bit / 16-bit /
   float8 types and ``saturate=0`` raise :class:`PlanError`.
+* ``SVMStep``    ai.onnx.ml SVMRegressor (SVR, one-class) and the two-class SVC form of
+                 SVMClassifier, kernels LINEAR / POLY / RBF / SIGMOID -> ``svm`` on the f32 matrix
+                 cores (csrc/kernels/svm.hip), f32 whatever ``precision`` says. A Scaler / constant
+                 affine on its input folds into the step's input stage, a following constant Mul /
+                 Add / Neg and a Sigmoid into its epilogue (exclusive, single-use values only, as the
+                 tree Sigmoid fold); a classifier is lowered to its positive column. Up to
+                 ``SVM_MAX_F`` = 256 input columns; POLY with an integral degree in [0, 16]; post
+                 transforms NONE and LOGISTIC; anything else raises :class:`PlanError`.
 * ``BatchNormalization`` (inference) is a per-column affine and folds like ``Scaler``;
   ``Dropout`` is folded away.
 * ai.onnx.ml ``LinearClassifier`` / ``LinearRegressor`` (post NONE / LOGISTIC; a two-class
@@ -298,6 +306,8 @@ class Plan:
                 parts.append(f"qdense({s.x_type}:{s.k}->{s.n},{s.act},{s.out_q[2] if s.out_q else 'f32'})")
             elif s.kind in ("quant", "dequant"):
                 parts.append(f"{s.kind}({s.width},{s.qtype})")
+            elif s.kind == "svm":
+                parts.append(f"svm({s.in_dim},{s.n_sv},{s.kernel})")
             else:
                 parts.append(f"{s.kind}(I={s.in_dim},H={s.hidden}{',lens' if getattr(s, 'masked', False) else ''})")
         return " -> ".join(parts)
@@ -413,6 +423,117 @@ class DequantStep:
         return self.width
 
 
+SVM_KERNELS = ("LINEAR", "POLY", "RBF", "SIGMOID")   # csrc/runtime/svm.h Kernel codes
+SVM_MAX_F = 256          # input columns the device kernel stages (csrc/kernels/launch.h SVM_MAX_F)
+SVM_MAX_DEGREE = 16      # POLY degrees run as a fixed multiply sequence up to here
+
+
+@dataclass
+class SVMStep:
+    """ai.onnx.ml SVMRegressor / two-class SVMClassifier (csrc/kernels/svm.hip), f32 whatever the
+    plan's precision: dec = sum_i coef[i] K(x', sv_i) + rho on x' = x * in_scale + in_shift, then the
+    folded output stage, in this order: Platt p = 1 / (1 + exp(a dec + b)) (``platt_flip``: 1 - p,
+    the classifier's positive column), the one-class sign, v * post_scale + post_shift, ``act``.
+    The device takes up to ``SVM_MAX_F`` = 256 input columns (its X tile lives in LDS)."""
+    kernel: str              # LINEAR | POLY | RBF | SIGMOID
+    gamma: float
+    coef0: float
+    degree: int              # POLY only
+    n_sv: int
+    in_dim: int
+    sv_np: np.ndarray        # [S, F] f32
+    coef_np: np.ndarray      # [S] f32
+    rho: float
+    in_scale: Optional[np.ndarray] = None   # [F] float64: a folded Scaler / constant affine
+    in_shift: Optional[np.ndarray] = None
+    post_scale: float = 1.0
+    post_shift: float = 0.0
+    act: str = "none"        # none | sigmoid
+    platt: Optional[Tuple[float, float]] = None
+    platt_flip: bool = False
+    one_class: bool = False
+    sv: Any = None           # device tables (svm_tables)
+    coef: Any = None
+    sv_norm: Any = None
+    scale: Any = None
+    shift: Any = None
+    kind: str = "svm"
+    src: Optional[int] = None
+
+    @property
+    def out_width(self) -> int:
+        return 1
+
+
+def svm_centre(sv: np.ndarray) -> np.ndarray:
+    """The point an RBF step's vectors and inputs are moved by: per column the mean of the support
+    vectors, snapped to a power-of-two grid no finer than their largest distance from it (the mean
+    itself when they all agree). The residual offset stays within the vectors' spread, and ``s - c``
+    is exact for vectors with short mantissas (integer features stay integers)."""
+    sv64 = np.asarray(sv, np.float64)
+    mean = sv64.mean(axis=0)
+    dev = np.abs(sv64 - mean).max(axis=0)
+    grid = np.exp2(np.ceil(np.log2(np.where(dev > 0, dev, 1.0))))
+    return np.where(dev > 0, np.round(mean / grid) * grid, mean)
+
+
+def svm_tables(s: SVMStep) -> Dict[str, Any]:
+    """Host tables of a kernel machine, as torch tensors on the CPU (no GPU needed):
+
+    * ``sv``      f32 [S_pad(64), f_pad(32)], zero padded; ``coef`` f32 [S_pad];
+    * ``scale`` / ``shift`` f32 [f_pad]: the input affine (ones / zeros without one);
+    * ``sv_norm`` f32 [S_pad] (RBF only): |s_i|^2 of the table's rows, summed in float64, rounded once.
+
+    RBF runs as |x'|^2 + |s|^2 - 2 x'.s. To keep that away from cancellation on unscaled features
+    the problem is centred first: the table holds s_i - c and the shift in_shift - c, c =
+    :func:`svm_centre` (distances do not change). The other kernels are not centred."""
+    import torch
+    S, F = s.sv_np.shape
+    sv = s.sv_np.astype(np.float64)
+    scale = np.ones(F) if s.in_scale is None else np.broadcast_to(np.asarray(s.in_scale, np.float64), (F,))
+    shift = np.zeros(F) if s.in_shift is None else np.broadcast_to(np.asarray(s.in_shift, np.float64), (F,))
+    if s.kernel == "RBF":
+        c = svm_centre(sv)
+        sv, shift = sv - c, shift - c
+    s_pad, f_pad = -(-S // 64) * 64, -(-F // 32) * 32
+    tab = np.zeros((s_pad, f_pad), np.float32)
+    tab[:S, :F] = sv
+    coef = np.zeros(s_pad, np.float32)
+    coef[:S] = s.coef_np
+    sc, sh = np.zeros(f_pad, np.float32), np.zeros(f_pad, np.float32)
+    sc[:F], sh[:F] = scale, shift
+    out = dict(sv=torch.from_numpy(tab), coef=torch.from_numpy(coef), scale=torch.from_numpy(sc),
+               shift=torch.from_numpy(sh), sv_norm=None)
+    if s.kernel == "RBF":
+        out["sv_norm"] = torch.from_numpy((tab.astype(np.float64) ** 2).sum(axis=1).astype(np.float32))
+    return out
+
+
+def validate_svm(s: SVMStep) -> None:
+    """Host check of a kernel machine before it reaches the device: a known kernel, table shapes
+    that agree, finite values, and sizes inside what svm.hip is built for."""
+    if s.kernel not in SVM_KERNELS:
+        raise PlanError(f"svm: unknown kernel type {s.kernel!r}")
+    if s.sv_np.ndim != 2 or s.sv_np.shape != (s.n_sv, s.in_dim) or s.coef_np.shape != (s.n_sv,) or s.n_sv < 1:
+        raise PlanError("svm: support vectors must be [S, F] with one coefficient each")
+    if not 1 <= s.in_dim <= SVM_MAX_F:
+        raise PlanError(f"svm: {s.in_dim} input columns (the device kernel takes 1 .. {SVM_MAX_F})")
+    if s.kernel == "POLY" and (int(s.degree) != s.degree or not 0 <= s.degree <= SVM_MAX_DEGREE):
+        raise PlanError(f"svm: POLY degree {s.degree} (an integer in [0, {SVM_MAX_DEGREE}])")
+    if s.act not in ("none", "sigmoid"):
+        raise PlanError(f"svm: activation {s.act!r}")
+    for name, t in (("support vectors", s.sv_np), ("coefficients", s.coef_np), ("in_scale", s.in_scale),
+                    ("in_shift", s.in_shift)):
+        if t is not None and not np.isfinite(np.asarray(t, np.float64)).all():
+            raise PlanError(f"svm: non-finite {name}")
+    for name, t in (("in_scale", s.in_scale), ("in_shift", s.in_shift)):
+        if t is not None and np.asarray(t).size not in (1, s.in_dim):
+            raise PlanError(f"svm: {name} must hold one value per input column")
+    scal = [s.gamma, s.coef0, s.rho, s.post_scale, s.post_shift] + list(s.platt or ())
+    if not np.isfinite(np.asarray(scal, np.float64)).all():
+        raise PlanError("svm: non-finite parameters")
+
+
 def step_qtype(s) -> Optional[str]:
     """The quantised type of a step's output buffer (None: a float buffer)."""
     if s.kind == "quant":
@@ -507,7 +628,12 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
     one's, when it has no activation), a constant Add after MatMul into its bias, Relu /
     Sigmoid / Tanh into the dense epilogue. Two branches meet in a :class:`JoinStep`."""
     N = native()
-    ex = N.Executor(model)
+    try:
+        ex = N.Executor(model)
+    except RuntimeError as e:   # a malformed or out-of-scope kernel machine: the reader's message
+        if str(e).startswith("SVM"):
+            raise PlanError(str(e)) from e
+        raise
     nodes = model.nodes()
     index = {id(n): i for i, n in enumerate(nodes)}
     inputs = {v[0]: v for v in model.inputs()}
@@ -646,6 +772,10 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
             st.w_np = np.ascontiguousarray(st.w_np * sc[:, None], np.float32)
             b = np.zeros(st.n) if st.b_np is None else st.b_np.astype(np.float64)
             st.b_np = (b * sc + sh).astype(np.float32)
+            nv = _Val(v.step, w, ml_col=v.ml_col, cpu_col=v.cpu_col)
+        elif st is not None and st.kind == "svm" and st.act == "none" and v.exclusive and w == 1:
+            # a constant Mul / Add / Neg on a kernel machine's value: its epilogue
+            st.post_scale, st.post_shift = st.post_scale * sc[0], st.post_shift * sc[0] + sh[0]
             nv = _Val(v.step, w, ml_col=v.ml_col, cpu_col=v.cpu_col)
         else:
             i = emit(DenseStep(n=w, k=w, act="none", w_np=np.diag(sc).astype(np.float32),
@@ -937,6 +1067,9 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
             elif (st is not None and st.kind == "tree" and op == "Sigmoid" and st.post == 0 and st.binary_class < 0
                   and v.exclusive and single_use(x)):
                 st.post = 1
+            elif (st is not None and st.kind == "svm" and op == "Sigmoid" and st.act == "none"
+                  and v.exclusive and single_use(x)):
+                st.act = "sigmoid"
             else:   # after a join, a tree, another activation, or on a value with other readers
                 row_act(x, n["outputs"][0], op, op.lower())
                 continue
@@ -1176,6 +1309,48 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
             else:
                 vals[n["outputs"][0]] = scores
             continue
+        if op == "Neg":
+            affine(x, n["outputs"][0], op, scale=-1.0)
+            continue
+        if op in ("SVMClassifier", "SVMRegressor"):
+            info = ex.svm_info(index[id(n)])
+            v = get(x, op)   # a pending Scaler / constant affine becomes the step's input stage
+            F_, S_ = int(info["n_feat"]), int(info["n_sv"])
+            if v.width > 0 and v.width != F_:
+                raise PlanError(f"{op}: support vectors have {F_} columns, the input {v.width}")
+            if F_ > SVM_MAX_F:
+                raise PlanError(f"{op}: {F_} input columns (> {SVM_MAX_F}) are CPU-only")
+            kern = SVM_KERNELS[int(info["kernel"])]
+            deg = float(info["degree"])
+            if kern == "POLY" and (deg != int(deg) or not 0 <= deg <= SVM_MAX_DEGREE):
+                raise PlanError(f"{op}: POLY degree {deg:g} is CPU-only (the device takes integers in [0, {SVM_MAX_DEGREE}])")
+            post = POST[int(info["post"])]
+            if post not in LINEAR_POST:
+                raise PlanError(f"{op}: post_transform {post} is CPU-only")
+            for what_, t in (("scale", v.scale), ("shift", v.shift)):
+                if t is not None and len(t) not in (1, F_):
+                    raise PlanError(f"{op}: {len(t)} per-column input constants for {F_} columns")
+            ss = SVMStep(kernel=kern, gamma=float(info["gamma"]), coef0=float(info["coef0"]),
+                         degree=int(deg) if kern == "POLY" else 0, n_sv=S_, in_dim=F_,
+                         sv_np=np.ascontiguousarray(info["sv"], np.float32),
+                         coef_np=np.ascontiguousarray(info["coef"], np.float32), rho=float(info["rho"]),
+                         in_scale=None if v.scale is None else np.array(np.broadcast_to(v.scale, (F_,)), np.float64),
+                         in_shift=None if v.shift is None else np.array(np.broadcast_to(v.shift, (F_,)), np.float64))
+            if info["classifier"]:
+                # the positive column (classlabels[1]): 1 - p0 with Platt, else post(-dec)
+                if info["platt"]:
+                    ss.platt, ss.platt_flip = (float(info["prob_a"]), float(info["prob_b"])), True
+                else:
+                    ss.post_scale, ss.act = -1.0, LINEAR_POST[post]
+                idx = emit(ss, v.step)
+                vals[n["outputs"][0]] = _Val(idx, 1, label=True)
+                if len(n["outputs"]) > 1 and n["outputs"][1]:
+                    vals[n["outputs"][1]] = _Val(idx, 1, ml_col=0, cpu_col=1, narrowed=True)
+            else:
+                ss.one_class, ss.act = bool(info["one_class"]), LINEAR_POST[post]
+                idx = emit(ss, v.step)
+                vals[n["outputs"][0]] = _Val(idx, 1)
+            continue
         if op == "Scaler":
             off = np.asarray(a.get("offset", [0.0]), np.float64).ravel()
             sc = np.asarray(a.get("scale", [1.0]), np.float64).ravel()
@@ -1205,7 +1380,7 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
     fam = model.metadata.get("family", "")
     if not fam:
         kinds = [s.kind for s in steps]
-        fam = ("gbdt" if kinds == ["tree"] else "stacked" if kinds and kinds[0] == "tree"
+        fam = ("svm" if kinds == ["svm"] else "gbdt" if kinds == ["tree"] else "stacked" if kinds and kinds[0] == "tree"
                else "gru" if "gru" in kinds else "lstm" if "lstm" in kinds else "mlp")
     plan = Plan(family=fam, in_width=in_width, steps=steps, out_width=fv.width, ml_col=fv.ml_col,
                 metadata=dict(model.metadata), input_name=input_name, output_name=output_name,
@@ -1243,6 +1418,8 @@ def executor_output(model, default_output: str = "output") -> Tuple[int, str]:
     if n is not None and n["op_type"] == "LinearClassifier":
         icpt = np.asarray(n["attrs"].get("intercepts", []))
         col = 1 if len(icpt) in (1, 2) else 0
+    elif n is not None and n["op_type"] == "SVMClassifier":
+        col = 1
     elif n is not None and n["op_type"] == "TreeEnsembleClassifier":
         col = 1 if len(np.asarray(n["attrs"].get("classlabels_int64s", n["attrs"].get("classlabels_strings", [])))) == 2 else 0
     return col, name
@@ -1409,6 +1586,11 @@ def to_device(plan: Plan, device, precision: str = "fp32") -> Plan:
             s.w1 = (_f32_padded(s.w1_np, k_mult=32) if precision == "fp32" else pad(s.w1_np)).to(device)
             s.b1 = None if s.b1_np is None else torch.from_numpy(np.ascontiguousarray(s.b1_np)).to(device)
             s.w2 = torch.from_numpy(s.w2_np).to(device)
+        elif s.kind == "svm":
+            validate_svm(s)   # before any upload
+            t = svm_tables(s)
+            s.sv, s.coef, s.scale, s.shift = (t[k].to(device) for k in ("sv", "coef", "scale", "shift"))
+            s.sv_norm = None if t["sv_norm"] is None else t["sv_norm"].to(device)
         elif s.kind == "qdense":
             t = qdense_tables(s)
             s.w8, s.corr, s.mult, s.b = (t[k].to(device) for k in ("w8", "corr", "mult", "bias"))

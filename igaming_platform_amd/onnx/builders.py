@@ -570,11 +570,56 @@ def qdq_mlp(widths=(30, 64, 1), seed: int = 15, act_int8: bool = False, per_chan
                  metadata={"family": family, "format": "qdq", "layers": str(len(ws))})
 
 
+def svm(n_features: int = 30, n_sv: int = 100, kernel: str = "RBF", op: str = "regressor", seed: int = 16,
+        gamma: float = None, coef0: float = 0.5, degree: float = 3.0, one_class: bool = False, platt: bool = False,
+        post: str = "NONE", scaler: bool = False, integer: bool = False, tail: str = "none"):
+    """A random kernel machine, no fit: ``op`` "regressor" (SVMRegressor -> output [N, 1]) or
+    "classifier" (two-class SVMClassifier -> label [N], output [N, 2], optionally Platt-scaled).
+    ``integer``: small-integer support vectors and coefficients (with integer ``gamma`` / ``coef0``
+    the LINEAR and POLY values are exact in float32). ``tail`` "neg_sigmoid" appends Mul(-1) ->
+    Sigmoid to a regressor (the one-class risk score)."""
+    rng = np.random.default_rng(seed)
+    if integer:
+        sv = rng.integers(-3, 4, (n_sv, n_features)).astype(np.float32)
+        coef = rng.integers(-2, 3, n_sv).astype(np.float32)
+        rho = np.array([float(rng.integers(-2, 3))], np.float32)
+    else:
+        sv = rng.standard_normal((n_sv, n_features)).astype(np.float32)
+        coef = (rng.standard_normal(n_sv) * 0.5).astype(np.float32)
+        rho = (rng.standard_normal(1) * 0.1).astype(np.float32)
+    g = 1.0 / n_features if gamma is None else gamma
+    a = dict(kernel_type=kernel, kernel_params=np.array([g, coef0, degree], np.float32), support_vectors=sv.ravel(),
+             coefficients=coef, rho=rho, post_transform=post)
+    nodes = [_scaler(rng, n_features)] if scaler else []
+    x = "scaled" if scaler else "input"
+    ins = [value_info("input", S.FLOAT, ["N", n_features])]
+    meta = {"family": "svm", "kernel": kernel}
+    if op == "classifier":
+        n0 = max(1, n_sv // 2) if n_sv > 1 else 1
+        a.update(vectors_per_class=np.array([n0, n_sv - n0], np.int64), classlabels_ints=np.array([0, 1], np.int64))
+        if platt:
+            a.update(prob_a=np.array([-1.5], np.float32), prob_b=np.array([0.25], np.float32))
+        nodes.append(node("SVMClassifier", [x], ["label", "probabilities"], domain=ML_DOMAIN, **a))
+        nodes.append(node("ZipMap", ["probabilities"], ["output"], domain=ML_DOMAIN,
+                          classlabels_int64s=np.array([0, 1], np.int64)))
+        return model(nodes, ins, [value_info("label", S.INT64, ["N"]), value_info("output", S.FLOAT, ["N", 2])],
+                     name="svm_classifier", metadata=meta)
+    a.update(n_supports=n_sv, one_class=int(one_class))
+    inits = []
+    if tail == "neg_sigmoid":
+        nodes += [node("SVMRegressor", [x], ["dec"], domain=ML_DOMAIN, **a), node("Mul", ["dec", "minus_one"], ["neg"]),
+                  node("Sigmoid", ["neg"], ["output"])]
+        inits.append(tensor("minus_one", np.array([-1.0], np.float32)))
+    else:
+        nodes.append(node("SVMRegressor", [x], ["output"], domain=ML_DOMAIN, **a))
+    return model(nodes, ins, [value_info("output", S.FLOAT, ["N", 1])], inits, name="svm_regressor", metadata=meta)
+
+
 BUILDERS = {"qdq_mlp": qdq_mlp,
             "logistic": logistic, "gbdt": gbdt, "gbdt_v5": gbdt_v5, "stacked": stacked, "ltv_mlp": ltv_mlp, "gru": gru,
             "lstm": lstm, "torch_mlp": torch_mlp, "tabular_resnet": tabular_resnet,
             "sklearn_linear": sklearn_linear, "linear_regressor": linear_regressor,
-            "mlp_classifier": mlp_classifier, "wide_deep": wide_deep, "residual_mlp": residual_mlp}
+            "mlp_classifier": mlp_classifier, "wide_deep": wide_deep, "residual_mlp": residual_mlp, "svm": svm}
 
 
 def build(kind: str, **kw):

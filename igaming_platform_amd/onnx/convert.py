@@ -1,4 +1,4 @@
-"""scikit-learn tree ensembles -> ONNX ``ai.onnx.ml`` TreeEnsemble models.
+"""scikit-learn tree ensembles and kernel machines -> ONNX ``ai.onnx.ml`` models.
 
 Stands in for the reference's missing model export scripts (Makefile:215-225
 ``model-train``/``model-export``; the scripts are not in the repository) and is the
@@ -12,7 +12,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import schema as S
-from .writer import V5_AGGREGATE, V5_POST, model, node, tree_attrs, tree_attrs_v5, value_info
+from .writer import V5_AGGREGATE, V5_POST, model, node, tensor, tree_attrs, tree_attrs_v5, value_info
 
 
 def _tree_dict(tree, scale: float, k_index: int = 0, n_targets: int = 1):
@@ -115,3 +115,79 @@ def hist_gradient_boosting(est, n_features: int, input_name: str = "input", outp
     return model(nodes, [value_info(input_name, S.FLOAT, ["N", n_features])],
                  [value_info(output_name, S.FLOAT, ["N", 1])], name="sklearn_hgb", ml_opset=5,
                  metadata={"family": "gbdt", "source": "sklearn"})
+
+
+def svm(est, n_features: int, scaler=None, output: str = "auto", input_name: str = "input",
+        output_name: str = "output"):
+    """A fitted binary ``SVC``, ``SVR`` or ``OneClassSVM`` -> ONNX (``SVMClassifier`` / ``SVMRegressor``),
+    with an optional fitted ``StandardScaler`` as a ``Scaler`` node in front.
+
+    Reads ``support_vectors_``, the dual coefficients and intercept (``_dual_coef_`` / ``_intercept_``
+    for SVC, libsvm's orientation: K @ _dual_coef_ + _intercept_ = -decision_function, positive for
+    ``classes_[0]``; ``dual_coef_`` / ``intercept_`` for SVR and OneClassSVM, where it equals
+    decision_function), ``_gamma``, ``coef0``, ``degree``, ``n_support_`` and, when the SVC was fitted
+    with ``probability=True``, ``probA_`` / ``probB_``. Every number is rounded to float32.
+
+    The model score rises with risk:
+
+    * SVC -> SVMClassifier -> ZipMap: outputs ``label`` [N] and ``output`` [N, 2] in ``classes_``
+      order; the score is column 1, P(classes_[1]) by Platt scaling with probabilities, else
+      Sigmoid(-dec) (post_transform LOGISTIC);
+    * OneClassSVM -> SVMRegressor -> Mul(-1) -> Sigmoid: ``output`` [N, 1], an outlier scores towards 1;
+    * SVR -> SVMRegressor: ``output`` [N, 1], the raw value.
+
+    ``output``: "auto" as above; "raw" the bare operator (SVC: scores [dec, -dec] with no post
+    transform; OneClassSVM and SVR: dec); "label" OneClassSVM only: one_class = 1, +1 / -1."""
+    name = type(est).__name__
+    if name not in ("SVC", "SVR", "OneClassSVM"):
+        raise ValueError(f"svm: {name} is not converted (SVC, SVR, OneClassSVM)")
+    if output not in ("auto", "raw", "label") or (output == "label" and name != "OneClassSVM"):
+        raise ValueError(f"svm: output {output!r} for {name}")
+    kernel = str(est.kernel).upper()
+    if kernel not in ("LINEAR", "POLY", "RBF", "SIGMOID"):
+        raise ValueError(f"svm: kernel {est.kernel!r} is not converted")
+    sv = np.asarray(est.support_vectors_, np.float32)
+    if sv.ndim != 2 or sv.shape[1] != n_features:
+        raise ValueError("svm: support vectors do not match n_features (sparse fits are not converted)")
+    clf = name == "SVC"
+    if clf and len(est.classes_) != 2:
+        raise ValueError("only binary classifiers are converted")
+    coef = np.asarray(est._dual_coef_ if clf else est.dual_coef_, np.float32).ravel()
+    rho = np.asarray(est._intercept_ if clf else est.intercept_, np.float32).ravel()[:1]
+    a = dict(kernel_type=kernel, kernel_params=np.array([est._gamma, est.coef0, est.degree], np.float32),
+             support_vectors=sv.ravel(), coefficients=coef, rho=rho)
+    nodes = []
+    x = input_name
+    if scaler is not None:
+        mean = np.zeros(n_features) if getattr(scaler, "mean_", None) is None else scaler.mean_
+        std = np.ones(n_features) if getattr(scaler, "scale_", None) is None else scaler.scale_
+        nodes.append(node("Scaler", [x], ["scaled"], domain="ai.onnx.ml", offset=np.asarray(mean, np.float32),
+                          scale=(1.0 / np.asarray(std, np.float64)).astype(np.float32)))
+        x = "scaled"
+    meta = {"family": "svm", "source": "sklearn", "estimator": name}
+    ins = [value_info(input_name, S.FLOAT, ["N", n_features])]
+    if clf:
+        platt = output == "auto" and len(np.ravel(getattr(est, "probA_", []))) == 1
+        if platt:
+            a.update(prob_a=np.asarray(est.probA_, np.float32).ravel(), prob_b=np.asarray(est.probB_, np.float32).ravel())
+        labels = np.asarray(est.classes_)
+        ints = labels.dtype.kind in "iub"
+        a.update(vectors_per_class=np.asarray(est.n_support_, np.int64),
+                 post_transform="LOGISTIC" if output == "auto" and not platt else "NONE")
+        lab = (dict(classlabels_ints=labels.astype(np.int64)) if ints
+               else dict(classlabels_strings=[str(c) for c in labels]))
+        nodes.append(node("SVMClassifier", [x], ["label", "probabilities"], domain="ai.onnx.ml", **a, **lab))
+        zl = (dict(classlabels_int64s=labels.astype(np.int64)) if ints else dict(classlabels_strings=lab["classlabels_strings"]))
+        nodes.append(node("ZipMap", ["probabilities"], [output_name], domain="ai.onnx.ml", **zl))
+        return model(nodes, ins, [value_info("label", S.INT64, ["N"]), value_info(output_name, S.FLOAT, ["N", 2])],
+                     name="sklearn_svc", metadata=meta)
+    a.update(n_supports=int(sv.shape[0]), post_transform="NONE", one_class=int(output == "label"))
+    inits = []
+    if name == "OneClassSVM" and output == "auto":
+        nodes += [node("SVMRegressor", [x], ["dec"], domain="ai.onnx.ml", **a),
+                  node("Mul", ["dec", "minus_one"], ["neg"]), node("Sigmoid", ["neg"], [output_name])]
+        inits.append(tensor("minus_one", np.array([-1.0], np.float32)))
+    else:
+        nodes.append(node("SVMRegressor", [x], [output_name], domain="ai.onnx.ml", **a))
+    return model(nodes, ins, [value_info(output_name, S.FLOAT, ["N", 1])], inits,
+                 name="sklearn_" + name.lower(), metadata=meta)

@@ -445,6 +445,53 @@ def dequantize(X: torch.Tensor, Y: torch.Tensor, M: int, N: int, scale, zp: int,
     _quant_rows("dequantize", Y, X, M, N, scale, zp, qtype, 1, m_ptr)
 
 
+SVM_KERNELS = {"LINEAR": 0, "POLY": 1, "RBF": 2, "SIGMOID": 3}
+SVM_MAX_F = 256        # csrc/kernels/launch.h SVM_MAX_F
+SVM_MAX_DEGREE = 16
+
+
+def svm_tile(M: int) -> int:
+    """Rows per workgroup ``svm`` picks for a launch of ``M`` rows (16 | 32 | 64)."""
+    return int(_mod().svm_tile(int(M)))
+
+
+def svm(step, X: torch.Tensor, Y: torch.Tensor, M: int, m_ptr: Optional[torch.Tensor] = None, tile: int = 0) -> None:
+    """Kernel machine (svm.hip) of an uploaded models.plan.SVMStep: Y[:M, 0] = the step's value for
+    the rows X[:M, :F] (float32). ``tile`` forces the row tile (16 | 32 | 64; 0: by ``M``); a row's result
+    does not depend on it."""
+    dev = X.device
+    F, S = int(step.in_dim), int(step.n_sv)
+    if X.dim() != 2 or X.dtype != torch.float32 or Y.dim() != 2 or Y.dtype != torch.float32:
+        raise ValueError("svm: X and Y must be 2-D float32")
+    if not 1 <= F <= SVM_MAX_F or S < 1 or M < 0:
+        raise ValueError(f"svm: 1 <= F <= {SVM_MAX_F}, S >= 1, M >= 0")
+    if X.shape[1] < F or Y.shape[1] < 1 or X.shape[0] < M or Y.shape[0] < M:
+        raise ValueError("svm: operand shapes smaller than M / F")
+    if step.kernel not in SVM_KERNELS or step.act not in ("none", "sigmoid") or tile not in (0, 16, 32, 64):
+        raise ValueError("svm: kernel type / activation / tile")
+    if step.kernel == "POLY" and not 0 <= int(step.degree) <= SVM_MAX_DEGREE:
+        raise ValueError(f"svm: POLY degree must lie in [0, {SVM_MAX_DEGREE}]")
+    sv = step.sv
+    if (sv is None or sv.dim() != 2 or sv.shape[0] % 64 or sv.shape[1] % 32 or sv.shape[0] < S
+            or not F <= sv.shape[1] <= SVM_MAX_F):
+        raise ValueError("svm: the support vector table must be padded to [S_pad % 64 == 0, f_pad % 32 == 0]")
+    s_pad, f_pad = int(sv.shape[0]), int(sv.shape[1])
+    platt = 0 if step.platt is None else (2 if step.platt_flip else 1)
+    pa, pb = step.platt if step.platt is not None else (0.0, 0.0)
+    d = dict(X=_need(X, "X", torch.float32, device=dev), sv=_need(sv, "sv", torch.float32, s_pad * f_pad, device=dev),
+             coef=_need(step.coef, "coef", torch.float32, s_pad, device=dev),
+             sv_norm=(_need(step.sv_norm, "sv_norm", torch.float32, s_pad, device=dev) if step.kernel == "RBF" else None),
+             in_scale=_need(step.scale, "in_scale", torch.float32, f_pad, device=dev),
+             in_shift=_need(step.shift, "in_shift", torch.float32, f_pad, device=dev),
+             Y=_need(Y, "Y", torch.float32, device=dev), m_ptr=_opt(m_ptr, "m_ptr", dtype=torch.int32),
+             M=int(M), F=F, S=S, ldx=int(X.shape[1]), ldy=int(Y.shape[1]), f_pad=f_pad, sv_rows=s_pad,
+             kernel=SVM_KERNELS[step.kernel], degree=int(step.degree) if step.kernel == "POLY" else 0,
+             gamma=float(step.gamma), coef0=float(step.coef0), rho=float(step.rho), platt=platt,
+             prob_a=float(pa), prob_b=float(pb), one_class=int(bool(step.one_class)),
+             post_scale=float(step.post_scale), post_shift=float(step.post_shift), act=ACT[step.act], tile=int(tile))
+    _mod().svm(d, _stream())
+
+
 JOIN_OPS = {"add": 0, "concat": 1}
 
 
