@@ -492,6 +492,30 @@ PYBIND11_MODULE(_hipk, m) {
     if (a.op == ROW_ACT && (a.act < RA_RELU || a.act > RA_PRELU)) throw std::runtime_error("row_op: act code");
     launch_or_record([a](hipStream_t st) { launch_row(a, st); }, s, "row_op");
   });
+  m.attr("COL_MAX_IN") = COL_MAX_IN;
+  m.attr("COL_MAX_OUT") = COL_MAX_OUT;
+  m.attr("COL_RECORD_BYTES") = int(sizeof(ColRecord));
+  m.def("col_assemble", [](py::dict d, uintptr_t s) {
+    ColArgs a{};
+    a.X = ptr<const float*>(d, "X");
+    a.Y = ptr<void*>(d, "Y");
+    a.tab = ptr<const ColRecord*>(d, "tab");
+    a.m_ptr = ptr<const int32_t*>(d, "m_ptr");
+    a.M = geti(d, "M");
+    a.in_width = geti(d, "in_width");
+    a.out_width = geti(d, "out_width");
+    a.ldx = geti(d, "ldx");
+    a.ldy = geti(d, "ldy");
+    a.y_bf16 = geti(d, "y_bf16");
+    const int tab_records = geti(d, "tab_records");
+    if (!a.X || !a.Y || !a.tab) throw std::runtime_error("col_assemble: missing pointers");
+    if (a.M < 0 || a.in_width < 1 || a.in_width > COL_MAX_IN || a.out_width < 1 || a.out_width > COL_MAX_OUT)
+      throw std::runtime_error("col_assemble: sizes (M >= 0, 1 <= in_width <= 256, 1 <= out_width <= 4096)");
+    if (a.ldx < a.in_width || a.ldy < a.out_width) throw std::runtime_error("col_assemble: ldx >= in_width and ldy >= out_width");
+    if (tab_records < ((a.out_width + 3) & ~3) || (reinterpret_cast<uintptr_t>(a.tab) & 15))
+      throw std::runtime_error("col_assemble: the record table must be 16-byte aligned and padded to a multiple of 4 columns");
+    launch_or_record([a](hipStream_t st) { launch_col_assemble(a, st); }, s, "col_assemble");
+  });
 
   auto head_args = [](const py::dict& d) {
     HeadArgs a{};

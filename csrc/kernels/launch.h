@@ -318,6 +318,34 @@ struct RowArgs {
 };
 void launch_row(const RowArgs& a, hipStream_t st);
 
+// Column assembly (columns.hip, models/plan.py ColumnStep): Y[:M, :out_width] = a per-column program
+// of X[:M, :in_width]. One ColRecord per output column, evaluated in this order: x = X[r][src];
+// impute (x = hit ? value : x; hit = isnan(x) with COL_IMP_NAN, else x == replaced); the affine
+// (x - sub) * mul, an f32 subtract then an f32 multiply; the mode.
+enum ColMode : int32_t { COL_PASS = 0, COL_ONEHOT = 1, COL_BINARIZE = 2, COL_ZERO = 3 };  // flags & COL_MODE_MASK
+constexpr int32_t COL_MODE_MASK = 0xf, COL_IMPUTE = 0x10, COL_IMP_NAN = 0x20, COL_AFFINE = 0x40;
+constexpr int COL_MAX_IN = 256;     // widest input: the X tile lives in LDS
+constexpr int COL_MAX_OUT = 4096;
+constexpr int COL_TILE_ROWS = 32;   // rows per workgroup
+struct ColRecord {          // 32 bytes: two 16-byte loads
+  int32_t src;              // input column, < in_width
+  int32_t flags;            // ColMode | COL_IMPUTE | COL_IMP_NAN | COL_AFFINE
+  float replaced, value;    // impute
+  float sub, mul;           // affine
+  float arg;                // COL_ONEHOT: the category (truncf(x) == arg); COL_BINARIZE: the threshold (x > arg)
+  float pad;
+};
+struct ColArgs {
+  const float* X;           // [M][ldx] f32
+  void* Y;                  // [M][ldy] f32 or bf16
+  const ColRecord* tab;     // [round_up(out_width, 4)]; the padding records are COL_ZERO on column 0
+  const int32_t* m_ptr;     // live rows in device memory (nullable -> M)
+  int32_t M, in_width, out_width;
+  int32_t ldx, ldy;
+  int32_t y_bf16;
+};
+void launch_col_assemble(const ColArgs& a, hipStream_t st);
+
 // dense(N1) + act1 + dense(N1 -> 1) + act2 fused; W1 bf16 [N1_pad(64)][k_pad(32)]
 // ---- K5 ensemble + action + metrics
 struct HeadArgs {

@@ -8,6 +8,8 @@
 #include <set>
 #include <stdexcept>
 
+#include "columns.h"
+
 namespace igp::exec {
 namespace {
 
@@ -31,7 +33,7 @@ std::vector<float> as_float(const Tensor& t) {
 std::vector<int64_t> as_int(const Tensor& t) {
   if (t.dtype == INT64 || t.dtype == onnx::INT32) return t.i;
   std::vector<int64_t> r;
-  for (float v : t.f) r.push_back(int64_t(v));
+  for (float v : t.f) r.push_back(cols::float_to_int64(v));  // NaN / out of range: INT64_MIN, defined
   return r;
 }
 
@@ -852,6 +854,26 @@ std::map<std::string, Tensor> Executor::run(const std::map<std::string, Tensor>&
         const float s = sc.empty() ? 1.f : sc[sc.size() == 1 ? 0 : c];
         out.f[e] = (xf[e] - o) * s;
       }
+    } else if (op == "Imputer") {
+      out = cols::imputer(n, get(n.inputs.at(0)));
+    } else if (op == "Binarizer") {
+      out = cols::binarizer(n, get(n.inputs.at(0)));
+    } else if (op == "OneHotEncoder") {
+      out = cols::one_hot_encoder(n, get(n.inputs.at(0)));
+    } else if (op == "ArrayFeatureExtractor" || op == "Gather") {
+      if (n.inputs.empty()) throw std::runtime_error(op + ": needs a value and its indices");
+      const bool cst = n.inputs.size() > 1 && g.initializers.count(n.inputs[1]) > 0;
+      out = op == "Gather" ? cols::gather(n, get(n.inputs[0]), opt(n, 1), cst)
+                           : cols::array_feature_extractor(n, get(n.inputs[0]), opt(n, 1), cst);
+    } else if (op == "Slice") {
+      if (n.inputs.empty()) throw std::runtime_error("Slice: needs data, starts and ends");
+      bool cst = true;
+      for (size_t i = 1; i < n.inputs.size(); ++i) cst &= n.inputs[i].empty() || g.initializers.count(n.inputs[i]) > 0;
+      out = cols::slice(n, get(n.inputs[0]), opt(n, 1), opt(n, 2), opt(n, 3), opt(n, 4), cst);
+    } else if (op == "FeatureVectorizer") {
+      std::vector<const Tensor*> ts;
+      for (auto& in : n.inputs) ts.push_back(&get(in));
+      out = cols::feature_vectorizer(n, ts);
     } else if (op == "Normalizer") {
       // per row (last axis): MAX divides by the row maximum, L1 by sum |x|, L2 by sqrt(sum x^2);
       // a zero denominator leaves the row unchanged

@@ -144,7 +144,8 @@ class DeviceModel:
                                                           for j in cons)
             # bf16 plans hand bf16 activations to the MFMA layers reading them (joins, row steps and
             # QuantizeLinear pass them on / read them in the same dtype); fp32 plans stay f32
-            dt = (torch.bfloat16 if (s.kind in ("dense", "qdense", "dequant", "gru", "lstm", "join", "row")
+            # (a column step reads f32 only, so whatever feeds one stays f32; its own output follows the rule)
+            dt = (torch.bfloat16 if (s.kind in ("dense", "qdense", "dequant", "gru", "lstm", "join", "row", "cols")
                                      and feeds_mma and plan.precision == "bf16")
                   else torch.float32)
             if step_qtype(s) is not None:
@@ -246,6 +247,9 @@ class DeviceModel:
             elif s.kind == "row":  # layernorm / softmax / an activation with no dense layer to ride on
                 K.row_op(s.op, cur, out, bucket, s.width, act=s.act, p0=s.p0, p1=s.p1, eps=s.eps, gamma=s.gamma,
                          beta=s.beta, m_ptr=m_ptr)
+                fused_partial = None
+            elif s.kind == "cols":  # a ColumnTransformer front end: one launch assembles the estimator's input
+                K.col_assemble(s, cur, out, bucket, m_ptr=m_ptr)
                 fused_partial = None
             elif s.kind == "dense":
                 K.dense(cur, s.w, s.b, out, bucket, s.n, s.k, act=s.act, m_ptr=m_ptr)

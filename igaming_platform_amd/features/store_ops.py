@@ -99,11 +99,32 @@ def input_names(width: int):
 
 
 def plan_importance(plan, width: int) -> Dict[str, float]:
-    """Normalised importance per model input column of a compiled plan (models/plan.py)."""
+    """Normalised importance per model input column of a compiled plan (models/plan.py). Where a
+    column step on the model input (a ColumnTransformer front end) feeds the trees or the first
+    dense layer, assembled column j is credited to the input column its record reads."""
     score = np.zeros(width, np.float64)
-    trees = [s for s in plan.steps if s.kind == "tree"]
+    steps = list(plan.steps)
+
+    def reads(i):  # index of the step whose output step i reads (-1: the model input)
+        src = getattr(steps[i], "src", None)
+        return i - 1 if src is None else src
+
+    def credit(i, per_column):
+        """``per_column``: a score per column of the value step ``i`` reads."""
+        j = reads(i)
+        if j >= 0 and steps[j].kind == "cols" and reads(j) < 0:
+            c = steps[j]
+            src = np.array([r.src for r in c.records], np.int64)
+            col = np.zeros(len(src), np.float64)
+            k = min(len(src), len(per_column))
+            col[:k] = np.asarray(per_column, np.float64)[:k]
+            per_column = np.bincount(src, weights=col, minlength=width)
+        n = min(width, len(per_column))
+        score[:n] += np.asarray(per_column, np.float64)[:n]
+
+    trees = [(i, s) for i, s in enumerate(steps) if s.kind == "tree"]
     if trees:
-        for t in trees:
+        for ti, t in trees:
             if t.layout == "sparse":  # pointer layout: [N][4] int32 {meta, thr, left, right}, leaves mode 7
                 nodes = np.asarray(t.nodes_np, np.int32).reshape(-1, 4)
                 meta = nodes[:, 0].view(np.uint32)
@@ -115,17 +136,19 @@ def plan_importance(plan, width: int) -> Dict[str, float]:
                 # set offset, whatever float those bits spell
                 real = np.isfinite(nodes[:, 0]) | (((meta >> 16) & 7) == 6)
                 feat = meta[real] & 0xFFFF
-            score += np.bincount(feat.astype(np.int64), minlength=width)[:width]
+            credit(ti, np.bincount(feat.astype(np.int64), minlength=width))
     else:
-        first = next((s for s in plan.steps if s.kind in ("dense", "qdense", "head")), None)
-        if plan.steps and plan.steps[0].kind == "svm":
-            # a kernel machine: the weight vector of its linear part, |sum_i coef_i sv_i| per column
-            sv = plan.steps[0]
-            w = np.abs(sv.coef_np.astype(np.float64) @ sv.sv_np.astype(np.float64))
-            score[:min(width, w.size)] = w[:width]
+        fi = next((i for i, s in enumerate(steps) if s.kind in ("dense", "qdense", "head")), None)
+        first = None if fi is None else steps[fi]
+        # a kernel machine as the first step, or the first behind a column step on the model input
+        si = next((i for i, s in enumerate(steps[:2]) if s.kind == "svm"), None)
+        if si is not None and (si == 0 or (steps[0].kind == "cols" and reads(si) == 0)):
+            # the weight vector of its linear part, |sum_i coef_i sv_i| per column
+            sv = steps[si]
+            credit(si, np.abs(sv.coef_np.astype(np.float64) @ sv.sv_np.astype(np.float64)))
         elif first is not None:
             w = first.w1_np if first.kind == "head" else first.w_np   # [N, K]
-            score[:min(width, w.shape[1])] = np.abs(w).sum(axis=0)[:width]
+            credit(fi, np.abs(w).sum(axis=0))
     tot = score.sum()
     names = input_names(width)
     if tot <= 0:

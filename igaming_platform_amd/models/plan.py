@@ -52,6 +52,17 @@ steps:
                  tree Sigmoid fold); a classifier is lowered to its positive column. Up to
                  ``SVM_MAX_F`` = 256 input columns; POLY with an integral degree in [0, 16]; post
                  transforms NONE and LOGISTIC; anything else raises :class:`PlanError`.
+* ``ColumnStep`` the front end of a scikit-learn ``Pipeline(ColumnTransformer, estimator)``: any
+                 sub-graph of ai.onnx.ml Imputer, Scaler, OneHotEncoder, Binarizer,
+                 ArrayFeatureExtractor, FeatureVectorizer and ai.onnx Gather / Slice (feature axis,
+                 constant indices), Concat (axis 1) and Cast(int) -> OneHotEncoder is tracked as a
+                 *column view* - per column of the value, a record (source column of a base value,
+                 impute, (x - sub) * mul, pass | one-hot | binarize) - and becomes ONE
+                 ``col_assemble`` launch (csrc/kernels/columns.hip) when anything else reads it. An
+                 operator that does not fit the record's free stages materialises the view and
+                 starts a fresh one, so float arithmetic is never reordered and the step is
+                 bit-equal to the executor. Up to 256 base columns and 4096 assembled ones; string
+                 categories, ``zeros = 0`` and the int64 Imputer attributes raise :class:`PlanError`.
 * ``BatchNormalization`` (inference) is a per-column affine and folds like ``Scaler``;
   ``Dropout`` is folded away.
 * ai.onnx.ml ``LinearClassifier`` / ``LinearRegressor`` (post NONE / LOGISTIC; a two-class
@@ -308,6 +319,8 @@ class Plan:
                 parts.append(f"{s.kind}({s.width},{s.qtype})")
             elif s.kind == "svm":
                 parts.append(f"svm({s.in_dim},{s.n_sv},{s.kernel})")
+            elif s.kind == "cols":
+                parts.append(f"cols({s.in_width}->{s.out_width})")
             else:
                 parts.append(f"{s.kind}(I={s.in_dim},H={s.hidden}{',lens' if getattr(s, 'masked', False) else ''})")
         return " -> ".join(parts)
@@ -534,6 +547,103 @@ def validate_svm(s: SVMStep) -> None:
         raise PlanError("svm: non-finite parameters")
 
 
+COL_MODES = {"pass": 0, "onehot": 1, "binarize": 2, "zero": 3}   # csrc/kernels/launch.h ColMode
+COL_IMPUTE, COL_IMP_NAN, COL_AFFINE = 0x10, 0x20, 0x40          # ... and the ColRecord flag bits
+COL_MAX_IN = 256         # widest base value the kernel stages (csrc/kernels/launch.h COL_MAX_IN)
+COL_MAX_OUT = 4096
+COL_RECORD = np.dtype([("src", "<i4"), ("flags", "<i4"), ("replaced", "<f4"), ("value", "<f4"), ("sub", "<f4"),
+                       ("mul", "<f4"), ("arg", "<f4"), ("pad", "<f4")])   # launch.h ColRecord, 32 bytes
+
+
+@dataclass(frozen=True)
+class ColRec:
+    """One column of a column view: a function of column ``src`` of the base value, evaluated in
+    this order: impute (``imp`` = (replaced, value): x = hit ? value : x, hit = isnan(x) for a NaN
+    ``replaced``, else x == replaced), the affine (``aff`` = (sub, mul): (x - sub) * mul in f32, the
+    Scaler's own order), then ``mode``: pass | onehot (trunc(x) == arg) | binarize (x > arg) | zero."""
+    src: int
+    imp: Optional[Tuple[float, float]] = None
+    aff: Optional[Tuple[float, float]] = None
+    mode: str = "pass"
+    arg: float = 0.0
+
+    @property
+    def identity(self) -> bool:
+        return self.imp is None and self.aff is None and self.mode == "pass"
+
+
+@dataclass
+class ColumnStep:
+    """A sub-graph of column operators (Imputer, Scaler, OneHotEncoder, Binarizer,
+    ArrayFeatureExtractor / Gather / Slice, Concat / FeatureVectorizer: a scikit-learn
+    ColumnTransformer) as one launch of ``col_assemble`` (csrc/kernels/columns.hip): output column
+    j is ``records[j]`` of the producing value's row. f32 in; the arithmetic is the CPU executor's,
+    so the result is bit-equal to it."""
+    in_width: int
+    out_width: int
+    records: List[ColRec]
+    tab: Any = None          # device table (upload_columns)
+    tab_key: Any = None      # what the table was checked and built for: (in_width, out_width, id(records))
+    kind: str = "cols"
+    src: Optional[int] = None
+
+
+def column_table(s: ColumnStep) -> np.ndarray:
+    """The step's record table as the kernel reads it: one ``COL_RECORD`` per output column, padded
+    to a multiple of 4 columns with always-zero records."""
+    tab = np.zeros(-(-len(s.records) // 4) * 4, COL_RECORD)
+    tab["flags"] = COL_MODES["zero"]
+    for j, r in enumerate(s.records):
+        flags = COL_MODES[r.mode]
+        if r.imp is not None:
+            rep, val = np.float32(r.imp[0]), np.float32(r.imp[1])
+            flags |= COL_IMPUTE | (COL_IMP_NAN if np.isnan(rep) else 0)
+            tab[j]["replaced"], tab[j]["value"] = (0.0 if np.isnan(rep) else rep), val
+        if r.aff is not None:
+            flags |= COL_AFFINE
+            tab[j]["sub"], tab[j]["mul"] = np.float32(r.aff[0]), np.float32(r.aff[1])
+        tab[j]["src"], tab[j]["flags"], tab[j]["arg"] = r.src, flags, np.float32(r.arg)
+    return tab
+
+
+def check_columns(s: ColumnStep) -> None:
+    """Host check of a column step before it reaches the device: sizes inside what columns.hip is
+    built for, every source column inside the base value, known modes, finite constants where the
+    kernel compares or multiplies with them (an imputed value may be anything; a replaced value may
+    be NaN: that is the isnan test)."""
+    if not 1 <= int(s.in_width) <= COL_MAX_IN:
+        raise PlanError(f"cols: {s.in_width} input columns (the device kernel takes 1 .. {COL_MAX_IN})")
+    if not 1 <= int(s.out_width) <= COL_MAX_OUT or len(s.records) != s.out_width:
+        raise PlanError(f"cols: {s.out_width} output columns with {len(s.records)} records (1 .. {COL_MAX_OUT}, one each)")
+    for j, r in enumerate(s.records):
+        if int(r.src) != r.src or not 0 <= r.src < s.in_width:
+            raise PlanError(f"cols: column {j} reads source column {r.src} of {s.in_width}")
+        if r.mode not in COL_MODES:
+            raise PlanError(f"cols: column {j} has unknown mode {r.mode!r}")
+        if r.imp is not None and len(r.imp) != 2:
+            raise PlanError(f"cols: column {j} has a malformed impute stage {r.imp!r}")
+        if r.aff is not None and (len(r.aff) != 2 or not np.isfinite(np.asarray(r.aff, np.float32)).all()):
+            raise PlanError(f"cols: column {j} has a non-finite affine stage {r.aff!r}")
+        if r.mode in ("onehot", "binarize") and not np.isfinite(np.float32(r.arg)):
+            raise PlanError(f"cols: column {j} compares with a non-finite constant")
+        if r.mode == "onehot" and (np.float32(r.arg) != np.trunc(np.float32(r.arg)) or abs(float(r.arg)) >= 2.0 ** 63):
+            raise PlanError(f"cols: column {j} has one-hot category {r.arg!r} (an integer inside (-2^63, 2^63))")
+
+
+def columns_key(s: ColumnStep):
+    """What a step's uploaded table stands for; the launch wrapper compares it in O(1), so the
+    per-record check runs once, at upload."""
+    return (int(s.in_width), int(s.out_width), id(s.records))
+
+
+def upload_columns(s: ColumnStep, device) -> None:
+    """Check the step on the host (:func:`check_columns`), then build and upload its record table."""
+    import torch
+    check_columns(s)
+    s.tab = torch.from_numpy(column_table(s).view(np.uint8).reshape(-1, COL_RECORD.itemsize)).to(device)
+    s.tab_key = columns_key(s)
+
+
 def step_qtype(s) -> Optional[str]:
     """The quantised type of a step's output buffer (None: a float buffer)."""
     if s.kind == "quant":
@@ -606,6 +716,14 @@ class _Val:
     # ... and a DequantizeLinear of one, not yet materialised: a quantised Gemm reads the bytes of
     # ``step`` directly, any other reader gets a DequantStep first
     deq: Optional[Tuple[np.float32, int, str]] = None
+    # a pending column view: one ColRec per column of this value, each a function of one column of
+    # the base value (``step``'s output, ``base_width`` columns wide); materialised as a ColumnStep
+    # by the first reader that is no column operator
+    cols: Optional[List["ColRec"]] = None
+    base_width: int = -1
+    onehot3d: bool = False    # a OneHotEncoder output still shaped [N, C, n_cats] (Flatten / Reshape next)
+    int_cast: bool = False    # behind a Cast to an integer type: only a OneHotEncoder reads it
+    rank1: bool = False       # a Gather with a scalar index: [N]
 
 
 ALIAS_OPS = ("Identity", "Flatten", "Squeeze", "Unsqueeze", "Reshape", "ZipMap", "Cast", "Dropout")
@@ -738,7 +856,7 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
         steps.append(step)
         return len(steps) - 1
 
-    def get(name, what):
+    def get(name, what, rank1_ok=False):
         v = vals.get(name)
         if v is None:
             raise PlanError(f"{what}: value {name!r} is not computed by a lowered node")
@@ -754,7 +872,38 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
         if v.deq is not None:   # a reader other than a quantised Gemm: the DequantizeLinear runs on its own
             i = emit(DequantStep(v.width, *v.deq), v.step)
             v = vals[name] = _Val(i, v.width, ml_col=v.ml_col, cpu_col=v.cpu_col)
+        if v.cols is not None:  # a reader that is no column operator: the view becomes a step
+            v = vals[name] = materialise(v, what, rank1_ok)
         return v
+
+    materialised: Dict[int, Tuple[_Val, _Val]] = {}   # id(view) -> (the view, kept alive; its plain value)
+
+    def materialise(v: _Val, what, rank1_ok=False, int_ok=False) -> _Val:
+        """The plain value of a column view: a ColumnStep on its base, or the base itself when the
+        view is the identity over all of its columns."""
+        if v.onehot3d:
+            raise PlanError(f"{what}: a OneHotEncoder output [N, C, n_cats] must be flattened to [N, C * n_cats] "
+                            "(Flatten axis 1 / Reshape) before anything else reads it")
+        if v.int_cast and not int_ok:
+            raise PlanError(f"{what}: Cast to a non-float type is lowered only as the link to a OneHotEncoder")
+        if v.rank1 and not rank1_ok:
+            raise PlanError(f"{what}: a Gather with a scalar index ([N]) is lowered only into alias ops, Concat "
+                            "and FeatureVectorizer")
+        if id(v) in materialised:
+            return materialised[id(v)][1]
+        recs = v.cols
+        if v.base_width == len(recs) and all(r.identity and r.src == j for j, r in enumerate(recs)):
+            nv = _Val(v.step, len(recs), exclusive=v.exclusive, ml_col=v.ml_col, cpu_col=v.cpu_col)
+        else:
+            if v.base_width <= 0:
+                raise PlanError(f"{what}: column operators on a value of unknown width")
+            if v.base_width > COL_MAX_IN:
+                raise PlanError(f"{what}: column operators on {v.base_width} columns (> {COL_MAX_IN}) are CPU-only")
+            if not 1 <= len(recs) <= COL_MAX_OUT:
+                raise PlanError(f"{what}: column operators assemble {len(recs)} columns (1 .. {COL_MAX_OUT} on the device)")
+            nv = _Val(emit(ColumnStep(in_width=v.base_width, out_width=len(recs), records=list(recs)), v.step), len(recs))
+        materialised[id(v)] = (v, nv)
+        return nv
 
     def plain(name, what) -> _Val:
         """The value with its pending affine applied: folded into the producing dense layer when
@@ -821,6 +970,55 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
             raise PlanError(f"{what}: the width of its input must be known")
         i = emit(RowStep("act", v.width, act=act, p0=float(p0), p1=float(p1), gamma_np=gamma), v.step)
         vals[out] = _Val(i, v.width, ml_col=v.ml_col, cpu_col=v.cpu_col)
+
+    def identity_view(v: _Val) -> _Val:
+        return replace(v, cols=[ColRec(j) for j in range(v.width)], base_width=v.width)
+
+    def view(name, what, int_ok=False, rank1_ok=False) -> _Val:
+        """The value as a column view (an identity view starts on a plain value)."""
+        v = vals.get(name)
+        if v is None or v.cols is None:
+            v = plain(name, what)
+            if v.width <= 0:
+                raise PlanError(f"{what}: column operators on a value of unknown width")
+            return replace(identity_view(v), exclusive=v.exclusive and single_use(name))
+        if v.onehot3d or (v.int_cast and not int_ok) or (v.rank1 and not rank1_ok):
+            materialise(v, what)   # raises the matching refusal
+        return v
+
+    def fill(name, out, what, v, fits, stage):
+        """A per-column operator on the view ``v`` of ``name``: ``stage(rec, column)`` fills the next
+        free stage of every record. Where one does not fit (``fits(rec)``), the view is materialised
+        first and a fresh identity view starts on the result, so float arithmetic is never reordered."""
+        if not all(fits(r) for r in v.cols):
+            base = materialise(v, what, rank1_ok=True, int_ok=True)   # the float view behind a pending Cast
+            v = replace(identity_view(base), int_cast=v.int_cast, rank1=v.rank1)
+        vals[out] = replace(v, cols=[stage(r, j) for j, r in enumerate(v.cols)],
+                            exclusive=v.exclusive and single_use(name))
+
+    def select(name, out, what, idx, rank1=False):
+        v = view(name, what)
+        vals[out] = replace(v, cols=[v.cols[j] for j in idx], width=len(idx), rank1=rank1,
+                            exclusive=v.exclusive and single_use(name))
+
+    def int_indices(what, which, name, C, wrap):
+        """A constant integer index tensor of ``what`` (ONNX int32 / int64), checked against C columns."""
+        if not name or name not in raw_inits:
+            raise PlanError(f"{what}: {which} must be a constant (an initializer)")
+        if int(model.initializer_dtype(name)) not in ((6, 7) if wrap else (7,)):
+            raise PlanError(f"{what}: {which} must be an {'int32 / ' if wrap else ''}int64 tensor")
+        arr = np.asarray(model.initializer(name), np.int64)
+        idx = [int(j) for j in arr.ravel()]
+        for j in idx:
+            if not (-C if wrap else 0) <= j < C:
+                raise PlanError(f"{what}: index {j} outside the {C} columns")
+        return [j + C if j < 0 else j for j in idx], arr.ndim
+
+    def per_column(what, arr, C, name):
+        arr = np.asarray(arr, np.float32).ravel()
+        if arr.size not in (1, C):
+            raise PlanError(f"{what}: {arr.size} values in {name} for {C} columns (1 or one per column)")
+        return np.broadcast_to(arr, (C,))
 
     for n in order:
         op, a = n["op_type"], n["attrs"]
@@ -1031,6 +1229,129 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
             else:
                 raise PlanError("Div of a constant by a value is not lowered")
             continue
+        out0 = n["outputs"][0] if n["outputs"] else ""
+        if op in ("ArrayFeatureExtractor", "Gather"):
+            v = view(x, op)
+            if op == "Gather" and int(a.get("axis", 0)) not in (1, -1):
+                raise PlanError(f"Gather: axis {int(a.get('axis', 0))} is not lowered (the feature axis of a 2-D value only)")
+            idx, nd = int_indices(op, "the indices", ins[1] if len(ins) > 1 else "", v.width, wrap=op == "Gather")
+            if op == "Gather" and (nd > 1 or (nd == 0 and len(idx) != 1)):
+                raise PlanError("Gather: the indices must be a scalar or 1-D")
+            select(x, out0, op, idx, rank1=op == "Gather" and nd == 0)
+            continue
+        if op == "Slice":
+            if any(k in a for k in ("starts", "ends", "axes")):
+                raise PlanError("Slice: the attribute form (opset < 10) is not lowered")
+            v = view(x, op)
+            parts = []
+            for k, which in ((1, "starts"), (2, "ends"), (3, "axes"), (4, "steps")):
+                name_k = ins[k] if len(ins) > k else ""
+                if not name_k and k > 2:
+                    parts.append(None)
+                    continue
+                if name_k not in raw_inits or int(model.initializer_dtype(name_k)) not in (6, 7):
+                    raise PlanError(f"Slice: {which} must be a constant integer tensor (an initializer)")
+                parts.append([int(j) for j in np.asarray(model.initializer(name_k), np.int64).ravel()])
+            starts, ends, axes, steps_ = parts
+            axes = list(range(len(starts))) if axes is None else axes
+            steps_ = [1] * len(starts) if steps_ is None else steps_
+            if not len(starts) == len(ends) == len(axes) == len(steps_):
+                raise PlanError("Slice: starts, ends, axes and steps differ in length")
+            idx, C, cut = list(range(v.width)), v.width, False
+            for s_, e_, ax, st_ in zip(starts, ends, axes, steps_):
+                if st_ == 0 or ax not in (0, 1, -1, -2):
+                    raise PlanError(f"Slice: step {st_} on axis {ax} of a 2-D value")
+                if ax in (0, -2):   # the row axis: N is symbolic, so only the explicit full range
+                    if s_ != 0 or st_ != 1 or e_ < 2 ** 31 - 1:
+                        raise PlanError("Slice: only the last axis may be cut (axis 0 must keep its full range)")
+                    continue
+                if cut:
+                    raise PlanError("Slice: the last axis is named twice")
+                cut = True
+                s_, e_ = (s_ + C if s_ < 0 else s_), (e_ + C if e_ < 0 else e_)
+                if st_ > 0:
+                    idx = list(range(min(max(s_, 0), C), min(max(e_, 0), C), st_))
+                else:
+                    idx = list(range(min(max(s_, 0), C - 1), min(max(e_, -1), C - 1), st_))
+            select(x, out0, op, idx)
+            continue
+        if op == "Imputer":
+            if "imputed_value_int64s" in a or "replaced_value_int64" in a:
+                raise PlanError("Imputer: the int64 attributes are not lowered")
+            v = view(x, op)
+            val = per_column(op, a.get("imputed_value_floats", []), v.width, "imputed_value_floats")
+            rep = float(np.float32(a.get("replaced_value_float", 0.0)))
+            fill(x, out0, op, v, lambda r: r.identity,
+                 lambda r, j: replace(r, imp=(rep, float(val[j]))))
+            continue
+        if op == "Scaler" and x in vals and vals[x].cols is not None:
+            # on a view: the record's affine stage, in the Scaler's own f32 order (no float64 folding)
+            v = view(x, op)
+            off = per_column(op, a.get("offset", [0.0]), v.width, "offset")
+            sc = per_column(op, a.get("scale", [1.0]), v.width, "scale")
+            fill(x, out0, op, v, lambda r: r.aff is None and r.mode == "pass",
+                 lambda r, j: replace(r, aff=(float(off[j]), float(sc[j]))))
+            continue
+        if op == "Binarizer":
+            v = view(x, op)
+            thr = float(np.float32(a.get("threshold", 0.0)))
+            fill(x, out0, op, v, lambda r: r.mode == "pass", lambda r, j: replace(r, mode="binarize", arg=thr))
+            continue
+        if op == "OneHotEncoder":
+            if "cats_strings" in a:
+                raise PlanError("OneHotEncoder: cats_strings (string categories) is not lowered")
+            cats = [int(c) for c in np.asarray(a.get("cats_int64s", []), np.int64).ravel()]
+            if not cats:
+                raise PlanError("OneHotEncoder: cats_int64s is required")
+            if int(a.get("zeros", 1)) == 0:
+                raise PlanError("OneHotEncoder: zeros = 0 (an unmatched value is an error) is CPU-only")
+            if any(c == -2 ** 63 for c in cats):
+                raise PlanError("OneHotEncoder: a category equal to INT64_MIN is not lowered")
+            v = view(x, op, int_ok=True, rank1_ok=True)
+            if not all(r.mode == "pass" for r in v.cols):
+                base = materialise(v, op, rank1_ok=True, int_ok=True)
+                v = replace(identity_view(base), rank1=v.rank1)
+            # the category as the f32 value it equals; one no f32 represents can never match an f32 input
+            f32 = [float(np.float32(c)) for c in cats]
+            recs = [replace(r, mode="onehot", arg=f) if int(f) == c else replace(r, mode="zero")
+                    for r in v.cols for c, f in zip(cats, f32)]
+            vals[out0] = replace(v, cols=recs, width=len(recs), int_cast=False, rank1=False, onehot3d=not v.rank1,
+                                 exclusive=v.exclusive and single_use(x))
+            continue
+        if op in ("Concat", "FeatureVectorizer"):
+            vs = [vals.get(i) for i in ins]
+            fv_op = op == "FeatureVectorizer"
+            if ((fv_op or int(a.get("axis", 0)) in (1, -1)) and vs
+                    and all(v is not None and v.cols is not None and not v.onehot3d and not v.int_cast
+                            and (fv_op or not v.rank1) for v in vs)
+                    and len({v.step for v in vs}) == 1):
+                # views over the same base: their records side by side, no step
+                if fv_op and "inputdimensions" in a:
+                    dims_ = [int(d) for d in np.asarray(a["inputdimensions"]).ravel()]
+                    if dims_ != [v.width for v in vs]:
+                        raise PlanError(f"FeatureVectorizer: inputdimensions {dims_} differ from the input widths "
+                                        f"{[v.width for v in vs]}")
+                recs = [r for v in vs for r in v.cols]
+                vals[out0] = replace(vs[0], cols=recs, width=len(recs), rank1=False,
+                                     exclusive=all(v.exclusive and single_use(i) for v, i in zip(vs, ins)))
+                continue
+        if op == "FeatureVectorizer":
+            # views over different bases, or views beside ordinary values: each is materialised, then
+            # the pairwise joins of Concat
+            if not ins or any(i in inits for i in ins):
+                raise PlanError("FeatureVectorizer is lowered on one or more computed values")
+            ws = [get(i, op, rank1_ok=True).width for i in ins]
+            if "inputdimensions" in a and [int(d) for d in np.asarray(a["inputdimensions"]).ravel()] != ws:
+                raise PlanError(f"FeatureVectorizer: inputdimensions differ from the input widths {ws}")
+            acc = plain(ins[0], op)
+            for nxt in ins[1:]:
+                vb = plain(nxt, op)
+                if acc.width <= 0 or vb.width <= 0:
+                    raise PlanError("FeatureVectorizer: input widths must be known")
+                idx = emit(JoinStep("concat", acc.step, vb.step, acc.width, vb.width), -1)
+                acc = _Val(idx, acc.width + vb.width)
+            vals[out0] = acc
+            continue
         if op == "Concat":
             if int(a.get("axis", 0)) not in (1, -1) or any(i in inits for i in ins) or len(ins) < 2:
                 raise PlanError("Concat is lowered along the feature axis of two or more branches")
@@ -1157,7 +1478,29 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
                 raise PlanError(f"bidirectional {steps[v.step].kind.upper()}: Y_h [2, N, H] must be transposed to "
                                 "[N, 2, H] before reshaping")
             if op == "Cast" and int(a.get("to", 1)) != 1:
+                # to int32 / int64 as the sole link between a column view and a OneHotEncoder: the
+                # encoder truncates the same way (NaN and out-of-range values match no category)
+                readers = [m for m in order if out0 in m["inputs"]]
+                if (int(a["to"]) not in (6, 7) or not readers or out0 in outs
+                        or any(m["op_type"] != "OneHotEncoder" for m in readers)):
+                    raise PlanError("Cast to a non-float type is not lowered")
+                v = replace(view(x, op, rank1_ok=True), int_cast=True)
+            elif op == "Cast" and v.int_cast:
                 raise PlanError("Cast to a non-float type is not lowered")
+            if v.cols is not None and v.onehot3d:
+                # [N, C, n_cats] -> [N, C * n_cats]: column-major then category, the records' order
+                shape = None
+                if op == "Reshape" and len(ins) > 1 and ins[1] in raw_inits:
+                    shape = [int(d) for d in np.asarray(model.initializer(ins[1])).ravel()]
+                if (op == "Flatten" and int(a.get("axis", 1)) == 1) or (
+                        shape is not None and len(shape) == 2 and shape[1] in (-1, v.width)
+                        and shape[0] in (0, -1) and shape != [-1, -1]):
+                    v = replace(v, onehot3d=False)
+                elif op not in ("Identity", "Dropout", "Cast"):
+                    raise PlanError(f"{op}: a OneHotEncoder output [N, C, n_cats] must be flattened to "
+                                    "[N, C * n_cats] (Flatten axis 1 / Reshape) before anything else reads it")
+            elif v.cols is not None and v.rank1 and op in ("Unsqueeze", "Reshape", "Flatten"):
+                v = replace(v, rank1=False)   # [N] -> [N, 1]
             vals[n["outputs"][0]] = v
             continue
         if op == "Transpose":
@@ -1365,8 +1708,9 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
     fv = vals.get(output_name)
     if fv is None or fv.label or fv.quant is not None:
         raise PlanError("the primary output must be a score / probability tensor")
-    if fv.deq is not None:
-        fv = get(output_name, "output")   # a trailing Q -> DQ: the DequantizeLinear is the last step
+    if fv.deq is not None or fv.cols is not None:
+        # a trailing Q -> DQ: the DequantizeLinear is the last step; a column view: its ColumnStep
+        fv = get(output_name, "output")
     if fv.scale is not None:
         fv = plain(output_name, "output")
     if not steps or fv.step != len(steps) - 1:
@@ -1379,7 +1723,7 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
         raise PlanError("sequence models are lowered as chains (GRU / LSTM layers + head) only")
     fam = model.metadata.get("family", "")
     if not fam:
-        kinds = [s.kind for s in steps]
+        kinds = [s.kind for s in steps if s.kind != "cols"]   # a column front end keeps the estimator's family
         fam = ("svm" if kinds == ["svm"] else "gbdt" if kinds == ["tree"] else "stacked" if kinds and kinds[0] == "tree"
                else "gru" if "gru" in kinds else "lstm" if "lstm" in kinds else "mlp")
     plan = Plan(family=fam, in_width=in_width, steps=steps, out_width=fv.width, ml_col=fv.ml_col,
@@ -1591,6 +1935,8 @@ def to_device(plan: Plan, device, precision: str = "fp32") -> Plan:
             t = svm_tables(s)
             s.sv, s.coef, s.scale, s.shift = (t[k].to(device) for k in ("sv", "coef", "scale", "shift"))
             s.sv_norm = None if t["sv_norm"] is None else t["sv_norm"].to(device)
+        elif s.kind == "cols":
+            upload_columns(s, device)   # the host check, then the table
         elif s.kind == "qdense":
             t = qdense_tables(s)
             s.w8, s.corr, s.mult, s.b = (t[k].to(device) for k in ("w8", "corr", "mult", "bias"))

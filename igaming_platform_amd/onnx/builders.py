@@ -615,7 +615,90 @@ def svm(n_features: int = 30, n_sv: int = 100, kernel: str = "RBF", op: str = "r
     return model(nodes, ins, [value_info("output", S.FLOAT, ["N", 1])], inits, name="svm_regressor", metadata=meta)
 
 
-BUILDERS = {"qdq_mlp": qdq_mlp,
+def columns(n_features: int = 30, n_trees: int = 20, depth: int = 4, seed: int = 18, final: str = "gbdt"):
+    """A random column program (what a scikit-learn ColumnTransformer exports to) in front of a small
+    GBDT: over a random permutation of the input columns,
+
+    * ~40 % numeric: Slice -> Imputer(NaN -> a constant per column) -> Scaler;
+    * two sentinel columns: Gather -> Imputer(replaced -999);
+    * two categorical columns, one through ArrayFeatureExtractor -> Cast(int64) -> OneHotEncoder ->
+      Flatten, one through a scalar-index Gather ([N]) -> OneHotEncoder ([N, n_cats]), with negative
+      categories;
+    * three flags: ArrayFeatureExtractor -> Binarizer;
+    * the rest passed through in reverse order (Slice with step -1);
+
+    joined by one Concat, then TreeEnsembleRegressor -> Sigmoid -> output [N, 1]. ``final`` "none"
+    ends at the assembled matrix instead (output [N, width]), "dense" at Gemm(width -> 8) -> Relu
+    (output [N, 8]). The input is first permuted by an
+    ArrayFeatureExtractor, so every branch selects from a view, not from the input itself."""
+    if n_features < 12:
+        raise ValueError("columns: at least 12 input columns")
+    rng = np.random.default_rng(seed)
+    nodes, inits = [], []
+
+    def const(name, arr):
+        inits.append(tensor(name, arr))
+        return name
+
+    perm = rng.permutation(n_features).astype(np.int64)
+    nodes.append(node("ArrayFeatureExtractor", ["input", const("perm", perm)], ["p"], domain=ML_DOMAIN))
+    n_num = max(2, int(0.4 * n_features))
+    # numeric: p[:, :n_num]
+    nodes.append(node("Slice", ["p", const("num_s", np.array([0], np.int64)), const("num_e", np.array([n_num], np.int64)),
+                                const("ax1", np.array([1], np.int64))], ["num"]))
+    nodes.append(node("Imputer", ["num"], ["num_i"], domain=ML_DOMAIN, replaced_value_float=float("nan"),
+                      imputed_value_floats=rng.uniform(0.2, 0.8, n_num).astype(np.float32)))
+    nodes.append(node("Scaler", ["num_i"], ["num_s_out"], domain=ML_DOMAIN,
+                      offset=rng.uniform(0.3, 0.7, n_num).astype(np.float32),
+                      scale=rng.uniform(0.5, 4.0, n_num).astype(np.float32)))
+    c = n_num
+    # sentinel columns
+    nodes.append(node("Gather", ["p", const("sen_idx", np.array([c, c + 1], np.int32))], ["sen"], axis=1))
+    nodes.append(node("Imputer", ["sen"], ["sen_i"], domain=ML_DOMAIN, replaced_value_float=-999.0,
+                      imputed_value_floats=np.array([0.5], np.float32)))
+    c += 2
+    # categorical: Cast + OneHotEncoder on [N, 1]; a scalar Gather + OneHotEncoder on [N]
+    cats_a = np.arange(-2, 4, dtype=np.int64)
+    cats_b = np.array([0, 1, 2, 3, 5, 8, 13], np.int64)
+    nodes.append(node("ArrayFeatureExtractor", ["p", const("cat_a_idx", np.array([c], np.int64))], ["cat_a"], domain=ML_DOMAIN))
+    nodes.append(node("Cast", ["cat_a"], ["cat_a_int"], to=S.INT64))
+    nodes.append(node("OneHotEncoder", ["cat_a_int"], ["hot_a3"], domain=ML_DOMAIN, cats_int64s=cats_a, zeros=1))
+    nodes.append(node("Flatten", ["hot_a3"], ["hot_a"], axis=1))
+    scalar = tensor("cat_b_idx", np.array([c + 1 - n_features], np.int64))
+    del scalar.dims[:]   # rank 0: the Gather drops the axis
+    inits.append(scalar)
+    nodes.append(node("Gather", ["p", "cat_b_idx"], ["cat_b"], axis=-1))
+    nodes.append(node("OneHotEncoder", ["cat_b"], ["hot_b"], domain=ML_DOMAIN, cats_int64s=cats_b))
+    c += 2
+    # flags
+    nodes.append(node("ArrayFeatureExtractor", ["p", const("flag_idx", np.array([c, c + 1, c + 2], np.int64))], ["flag"],
+                      domain=ML_DOMAIN))
+    nodes.append(node("Binarizer", ["flag"], ["flag_b"], domain=ML_DOMAIN, threshold=0.5))
+    c += 3
+    # the rest, last column first: p[:, -1 : c - 1 : -1]
+    nodes.append(node("Slice", ["p", const("rest_s", np.array([-1], np.int64)),
+                                const("rest_e", np.array([c - 1 - n_features], np.int64)), const("ax_last", np.array([-1], np.int64)),
+                                const("rest_step", np.array([-1], np.int64))], ["rest"]))
+    width = n_num + 2 + len(cats_a) + len(cats_b) + 3 + (n_features - c)
+    asm = "output" if final == "none" else "assembled"
+    nodes.append(node("Concat", ["num_s_out", "sen_i", "hot_a", "hot_b", "flag_b", "rest"], [asm], axis=1))
+    ins = [value_info("input", S.FLOAT, ["N", n_features])]
+    meta = {"family": "columns", "assembled_width": str(width)}
+    if final == "none":
+        return model(nodes, ins, [value_info("output", S.FLOAT, ["N", width])], inits, name="columns", metadata=meta)
+    if final == "dense":
+        inits += [tensor("W", (rng.standard_normal((width, 8)) * 0.3).astype(np.float32)),
+                  tensor("B", (rng.standard_normal(8) * 0.1).astype(np.float32))]
+        nodes += [node("Gemm", [asm, "W", "B"], ["z"]), node("Relu", ["z"], ["output"])]
+        return model(nodes, ins, [value_info("output", S.FLOAT, ["N", 8])], inits, name="columns_dense", metadata=meta)
+    trees = [random_complete_tree(rng, depth, width, 1, leaf_scale=0.15) for _ in range(n_trees)]
+    a = tree_attrs(trees, "target")
+    a.update(n_targets=1, aggregate_function="SUM", post_transform="NONE", base_values=np.array([-0.25], np.float32))
+    nodes += [node("TreeEnsembleRegressor", [asm], ["raw"], domain=ML_DOMAIN, **a), node("Sigmoid", ["raw"], ["output"])]
+    return model(nodes, ins, [value_info("output", S.FLOAT, ["N", 1])], inits, name="columns_gbdt", metadata=meta)
+
+
+BUILDERS = {"qdq_mlp": qdq_mlp, "columns": columns,
             "logistic": logistic, "gbdt": gbdt, "gbdt_v5": gbdt_v5, "stacked": stacked, "ltv_mlp": ltv_mlp, "gru": gru,
             "lstm": lstm, "torch_mlp": torch_mlp, "tabular_resnet": tabular_resnet,
             "sklearn_linear": sklearn_linear, "linear_regressor": linear_regressor,

@@ -1,4 +1,5 @@
-"""scikit-learn tree ensembles and kernel machines -> ONNX ``ai.onnx.ml`` models.
+"""scikit-learn tree ensembles, kernel machines and ColumnTransformer front ends -> ONNX
+``ai.onnx.ml`` models.
 
 Stands in for the reference's missing model export scripts (Makefile:215-225
 ``model-train``/``model-export``; the scripts are not in the repository) and is the
@@ -191,3 +192,158 @@ def svm(est, n_features: int, scaler=None, output: str = "auto", input_name: str
         nodes.append(node("SVMRegressor", [x], [output_name], domain="ai.onnx.ml", **a))
     return model(nodes, ins, [value_info(output_name, S.FLOAT, ["N", 1])], inits,
                  name="sklearn_" + name.lower(), metadata=meta)
+
+
+_FINAL = {"GradientBoostingClassifier": gradient_boosting, "GradientBoostingRegressor": gradient_boosting,
+          "RandomForestRegressor": random_forest, "HistGradientBoostingClassifier": hist_gradient_boosting,
+          "HistGradientBoostingRegressor": hist_gradient_boosting, "SVC": svm, "SVR": svm, "OneClassSVM": svm}
+
+
+def _column_indices(cols, n_features: int, name: str) -> np.ndarray:
+    """A ColumnTransformer column specifier (integer list, slice or boolean mask) as indices."""
+    if isinstance(cols, (str, bytes)) or callable(cols) or (
+            not isinstance(cols, slice) and np.asarray(cols).dtype.kind not in "iub"):
+        raise ValueError(f"column_pipeline: columns {cols!r} of {name!r} are not converted (integers, slices, masks)")
+    if not isinstance(cols, slice):
+        cols = np.asarray(cols)
+        if cols.ndim != 1 or (cols.dtype.kind == "b" and cols.size != n_features):
+            raise ValueError(f"column_pipeline: columns of {name!r} must be a list of indices or a mask over the input")
+    idx = np.arange(n_features)[cols]
+    return np.atleast_1d(idx).astype(np.int64)
+
+
+def column_pipeline(ct, n_features: int, final=None, input_name: str = "input", output_name: str = "output",
+                    final_args: Optional[dict] = None):
+    """A fitted ``ColumnTransformer`` (optionally with the fitted estimator ``final`` behind it: the two
+    halves of ``Pipeline(ct, final)``) -> ONNX.
+
+    Every branch becomes ``ArrayFeatureExtractor`` on the input followed by its transformers:
+    ``SimpleImputer`` -> ``Imputer`` (any strategy: the fitted ``statistics_``; ``missing_values`` NaN
+    or a number), ``StandardScaler`` -> ``Scaler``, ``MinMaxScaler`` -> ``Scaler`` with offset
+    ``-min_ / scale_``, ``OneHotEncoder`` (numeric integral categories, ``handle_unknown="ignore"``,
+    ``drop=None``) -> per column ``ArrayFeatureExtractor`` -> ``OneHotEncoder`` -> ``Flatten``, then
+    ``Concat``; ``Binarizer``; ``"passthrough"``; a ``Pipeline`` of these. ``"drop"`` branches and a
+    dropped remainder emit nothing. The branches meet in one ``Concat`` in the order of
+    ``ct.output_indices_``. Constants are rounded to float32.
+
+    ``final``: an estimator :func:`gradient_boosting`, :func:`random_forest`,
+    :func:`hist_gradient_boosting` or :func:`svm` converts; its graph reads the assembled value
+    (``final_args``: further keyword arguments of that function, such as ``output="raw"``).
+    Without it the model's output is the assembled matrix [N, width].
+
+    One difference: scikit-learn's encoder matches a category by equality, the ONNX operator after
+    truncation towards zero, so 2.5 matches category 2 here. Integral inputs encode as in sklearn."""
+    nodes: List = []
+    inits: List = []
+    parts: List[str] = []
+    width = 0
+    count = [0]
+
+    def fresh(stem: str) -> str:
+        count[0] += 1
+        return f"ct_{stem}_{count[0]}"
+
+    def extract(src: str, idx: np.ndarray) -> str:
+        name, out = fresh("idx"), fresh("cols")
+        inits.append(tensor(name, np.asarray(idx, np.int64)))
+        nodes.append(node("ArrayFeatureExtractor", [src, name], [out], domain="ai.onnx.ml"))
+        return out
+
+    def apply(tr, cur: str, k: int, where: str):
+        """Append the nodes of one fitted transformer on ``cur`` [N, k]; returns (value, width)."""
+        kind = type(tr).__name__
+        if isinstance(tr, str):
+            if tr == "passthrough":
+                return cur, k
+            raise ValueError(f"column_pipeline: transformer {tr!r} in {where!r} is not converted")
+        if kind == "FunctionTransformer" and tr.func is None:   # how a fitted remainder="passthrough" appears
+            return cur, k
+        if kind == "Pipeline":
+            for _, step in tr.steps:
+                cur, k = apply(step, cur, k, where)
+            return cur, k
+        if kind == "SimpleImputer":
+            stats = np.asarray(tr.statistics_, np.float64).ravel()
+            if getattr(tr, "add_indicator", False) or stats.size != k or not np.isfinite(stats).all():
+                raise ValueError(f"column_pipeline: SimpleImputer in {where!r} (add_indicator, or a column with no "
+                                 "observed value) is not converted")
+            mv = tr.missing_values
+            if not isinstance(mv, (int, float, np.integer, np.floating)) or isinstance(mv, bool):
+                raise ValueError(f"column_pipeline: SimpleImputer missing_values {mv!r} in {where!r} (NaN or a number)")
+            out = fresh("imputed")
+            nodes.append(node("Imputer", [cur], [out], domain="ai.onnx.ml", imputed_value_floats=stats.astype(np.float32),
+                              replaced_value_float=float(mv)))
+            return out, k
+        if kind in ("StandardScaler", "MinMaxScaler"):
+            if kind == "StandardScaler":
+                off = np.zeros(k) if tr.mean_ is None else np.asarray(tr.mean_, np.float64)
+                sc = np.ones(k) if tr.scale_ is None else 1.0 / np.asarray(tr.scale_, np.float64)
+            else:
+                if getattr(tr, "clip", False):
+                    raise ValueError(f"column_pipeline: MinMaxScaler(clip=True) in {where!r} is not converted")
+                sc = np.asarray(tr.scale_, np.float64)
+                off = -np.asarray(tr.min_, np.float64) / sc
+            out = fresh("scaled")
+            nodes.append(node("Scaler", [cur], [out], domain="ai.onnx.ml", offset=off.astype(np.float32),
+                              scale=sc.astype(np.float32)))
+            return out, k
+        if kind == "Binarizer":
+            out = fresh("binary")
+            nodes.append(node("Binarizer", [cur], [out], domain="ai.onnx.ml", threshold=float(tr.threshold)))
+            return out, k
+        if kind == "OneHotEncoder":
+            if tr.handle_unknown != "ignore" or tr.drop is not None or getattr(tr, "min_frequency", None) is not None \
+                    or getattr(tr, "max_categories", None) is not None:
+                raise ValueError(f"column_pipeline: OneHotEncoder in {where!r} must use handle_unknown='ignore', "
+                                 "drop=None and no infrequent categories")
+            outs, total = [], 0
+            for j, cats in enumerate(tr.categories_):
+                c = np.asarray(cats)
+                if c.dtype.kind not in "iuf" or not np.isfinite(c.astype(np.float64)).all() \
+                        or (c.astype(np.float64) != np.trunc(c.astype(np.float64))).any():
+                    raise ValueError(f"column_pipeline: OneHotEncoder in {where!r}: the categories of column {j} are "
+                                     "not all integral numbers")
+                col, hot, flat = extract(cur, np.array([j])), fresh("onehot"), fresh("hot")
+                nodes.append(node("OneHotEncoder", [col], [hot], domain="ai.onnx.ml", cats_int64s=c.astype(np.int64), zeros=1))
+                nodes.append(node("Flatten", [hot], [flat], axis=1))
+                outs.append(flat)
+                total += c.size
+            if len(outs) == 1:
+                return outs[0], total
+            out = fresh("encoded")
+            nodes.append(node("Concat", outs, [out], axis=1))
+            return out, total
+        raise ValueError(f"column_pipeline: transformer {kind} in {where!r} is not converted")
+
+    if type(ct).__name__ != "ColumnTransformer" or not hasattr(ct, "transformers_"):
+        raise ValueError("column_pipeline: a fitted ColumnTransformer is required")
+    for name, tr, cols in ct.transformers_:
+        idx = _column_indices(cols, n_features, name)
+        sl = ct.output_indices_[name]
+        if (isinstance(tr, str) and tr == "drop") or idx.size == 0:
+            if sl.stop != sl.start:
+                raise ValueError(f"column_pipeline: branch {name!r} should be empty")
+            continue
+        cur, k = apply(tr, extract(input_name, idx), int(idx.size), name)
+        if (sl.start, sl.stop) != (width, width + k):
+            raise ValueError(f"column_pipeline: branch {name!r} lands at columns {width}:{width + k}, "
+                             f"scikit-learn puts it at {sl.start}:{sl.stop}")
+        parts.append(cur)
+        width += k
+    if not parts:
+        raise ValueError("column_pipeline: the transformer keeps no column")
+    assembled = output_name if final is None else "ct_assembled"
+    nodes.append(node("Concat", parts, [assembled], axis=1) if len(parts) > 1 else node("Identity", parts, [assembled]))
+    ins = [value_info(input_name, S.FLOAT, ["N", n_features])]
+    meta = {"family": "columns", "source": "sklearn", "front_end": "ColumnTransformer", "assembled_width": str(width)}
+    if final is None:
+        return model(nodes, ins, [value_info(output_name, S.FLOAT, ["N", width])], inits, name="sklearn_columns",
+                     metadata=meta)
+    fname = type(final).__name__
+    if fname not in _FINAL:
+        raise ValueError(f"column_pipeline: final estimator {fname} is not converted ({', '.join(sorted(_FINAL))})")
+    sub = _FINAL[fname](final, width, input_name=assembled, output_name=output_name, **(final_args or {}))
+    ml_opset = max([int(o.version) for o in sub.opset_import if o.domain == "ai.onnx.ml"] + [3])
+    meta.update({p.key: p.value for p in sub.metadata_props})
+    return model(nodes + list(sub.graph.node), ins, list(sub.graph.output), inits + list(sub.graph.initializer),
+                 name="sklearn_pipeline", ml_opset=ml_opset, metadata=meta)

@@ -492,6 +492,39 @@ def svm(step, X: torch.Tensor, Y: torch.Tensor, M: int, m_ptr: Optional[torch.Te
     _mod().svm(d, _stream())
 
 
+COL_MAX_IN, COL_MAX_OUT, COL_RECORD_BYTES = 256, 4096, 32   # csrc/kernels/launch.h
+
+
+def col_assemble(step, X: torch.Tensor, Y: torch.Tensor, M: int, m_ptr: Optional[torch.Tensor] = None) -> None:
+    """Column assembly (columns.hip) of an uploaded models.plan.ColumnStep: Y[:M, :out_width] = the
+    step's per-column program of X[:M, :in_width]. X is float32 (any row stride >= in_width), Y
+    float32 or bfloat16."""
+    dev = Y.device
+    W, N = int(step.in_width), int(step.out_width)
+    if X.dim() != 2 or X.dtype != torch.float32:
+        raise ValueError("col_assemble: X must be 2-D float32")
+    if Y.dim() != 2 or Y.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("col_assemble: Y must be 2-D float32 or bfloat16")
+    if not 1 <= W <= COL_MAX_IN or not 1 <= N <= COL_MAX_OUT or M < 0:
+        raise ValueError(f"col_assemble: 1 <= in_width <= {COL_MAX_IN}, 1 <= out_width <= {COL_MAX_OUT}, M >= 0")
+    if X.shape[1] < W or Y.shape[1] < N or min(X.shape[0], Y.shape[0]) < M:
+        raise ValueError("col_assemble: operand shapes smaller than M / the widths")
+    tab = step.tab
+    n_pad = -(-N // 4) * 4
+    # the records were checked against these widths when the table was built (plan.upload_columns)
+    if tab is None or getattr(step, "tab_key", None) != (W, N, id(step.records)) or len(step.records) != N:
+        raise ValueError("col_assemble: the step's record table is not uploaded for these records and widths "
+                         "(models.plan.upload_columns)")
+    if tab.dtype != torch.uint8 or tab.dim() != 2 or tab.shape[1] != COL_RECORD_BYTES or tab.shape[0] < n_pad:
+        raise ValueError("col_assemble: the step's record table must be uint8 [round_up(out_width, 4), 32]")
+    d = dict(X=_need(X, "X", torch.float32, device=dev), Y=_need(Y, "Y", device=dev),
+             tab=_need(tab, "tab", torch.uint8, n_pad * COL_RECORD_BYTES, device=dev),
+             m_ptr=_opt(m_ptr, "m_ptr", dtype=torch.int32), M=int(M), in_width=W, out_width=N,
+             ldx=int(X.shape[1]), ldy=int(Y.shape[1]), y_bf16=int(Y.dtype == torch.bfloat16),
+             tab_records=int(tab.shape[0]))
+    _mod().col_assemble(d, _stream())
+
+
 JOIN_OPS = {"add": 0, "concat": 1}
 
 
