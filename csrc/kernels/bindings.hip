@@ -447,6 +447,88 @@ PYBIND11_MODULE(_hipk, m) {
     if (a.tile != 0 && a.tile != 16 && a.tile != 32 && a.tile != 64) throw std::runtime_error("svm: tile 0 | 16 | 32 | 64");
     launch_or_record([a](hipStream_t st) { launch_svm(a, st); }, s, "svm");
   });
+  m.attr("CONV_MAX_C") = CONV_MAX_C;
+  m.attr("CONV_MAX_K") = CONV_MAX_K;
+  m.attr("CONV_MAX_SPAN") = CONV_MAX_SPAN;
+  m.attr("CONV_MAX_T") = CONV_MAX_T;
+  m.def("conv1d", [](py::dict d, uintptr_t s) {
+    ConvArgs a{};
+    a.mode = geti(d, "mode");
+    a.X = ptr<const float*>(d, "X");
+    a.x_rows = geti(d, "x_rows");
+    a.ldx = geti(d, "ldx");
+    a.ev = ptr<const uint16_t*>(d, "ev");
+    a.rt = ptr<const AcctRT*>(d, "rt");
+    a.slots = ptr<const int32_t*>(d, "slots");
+    a.ev_ring = geti(d, "ev_ring");
+    a.I = geti(d, "I");
+    a.W = ptr<const float*>(d, "W");
+    a.bias = ptr<const float*>(d, "bias");
+    a.res = ptr<const float*>(d, "res");
+    a.Y = ptr<float*>(d, "Y");
+    a.ldr = geti(d, "ldr");
+    a.ldy = geti(d, "ldy");
+    a.m_ptr = ptr<const int32_t*>(d, "m_ptr");
+    a.n_rows = geti(d, "n_rows");
+    a.T = geti(d, "T");
+    a.c_in = geti(d, "c_in");
+    a.c_out = geti(d, "c_out");
+    a.k = geti(d, "k");
+    a.dil = geti(d, "dil");
+    a.pad_left = geti(d, "pad_left");
+    a.act = geti(d, "act");
+    a.act_post = geti(d, "act_post");
+    a.tt = geti(d, "tt");
+    a.per_tap = geti(d, "per_tap");
+    const int64_t w_numel = d.contains("w_numel") ? d["w_numel"].cast<int64_t>() : 0;
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    if (!a.W || !a.bias || !a.Y) throw std::runtime_error("conv1d: missing pointers");
+    if (a.n_rows < 0 || a.T < 1 || a.T > CONV_MAX_T || a.c_in < 1 || a.c_in > CONV_MAX_C || a.c_out < 1 ||
+        a.c_out > CONV_MAX_C || a.k < 1 || a.k > CONV_MAX_K || a.dil < 1 || a.dil * (a.k - 1) > CONV_MAX_SPAN)
+      throw std::runtime_error("conv1d: sizes (T <= 1024, channels <= 256, k <= 8, dil (k - 1) <= 128)");
+    if (a.pad_left < 0 || a.pad_left > a.dil * (a.k - 1)) throw std::runtime_error("conv1d: pad_left in [0, dil (k - 1)]");
+    if (a.act < 0 || a.act > 3 || a.act_post < 0 || a.act_post > 3) throw std::runtime_error("conv1d: act codes");
+    if ((a.tt != 0 && a.tt != 32 && a.tt != 64) || (a.per_tap != 0 && a.per_tap != 1)) throw std::runtime_error("conv1d: tt 0 | 32 | 64, per_tap 0 | 1");
+    const int64_t cp = (a.c_in + 15) & ~15, n_ob = (a.c_out + 15) >> 4;
+    if (w_numel < n_ob * a.k * cp * 16 || !al16(a.W) || !al16(a.bias))
+      throw std::runtime_error("conv1d: the packed weights must hold ceil(c_out / 16) * k * round_up(c_in, 16) * 16 floats, 16-byte aligned");
+    if (a.ldy % 4 || a.ldy < ((a.c_out + 3) & ~3) || !al16(a.Y)) throw std::runtime_error("conv1d: Y rows must be 16-byte aligned and hold c_out columns");
+    if (a.res && (a.ldr % 4 || a.ldr < ((a.c_out + 3) & ~3) || !al16(a.res))) throw std::runtime_error("conv1d: res rows must be 16-byte aligned and hold c_out columns");
+    if (a.mode == 0) {
+      if (!a.X || a.x_rows < a.n_rows || ((a.c_in & 3) == 0 && !al16(a.X)))
+        throw std::runtime_error("conv1d: dense input needs X [T][x_rows >= rows][c_in], 16-byte aligned when c_in is a multiple of 4");
+    } else if (a.mode == 1) {
+      if (!a.ev || !a.rt || !a.slots || a.ev_ring < a.T || a.I % 4 || a.I < a.c_in || (reinterpret_cast<uintptr_t>(a.ev) & 7))
+        throw std::runtime_error("conv1d: ring input needs ev, rt, slots, ev_ring >= T and c_in <= I (a multiple of 4)");
+    } else if (a.mode == 2) {
+      if (!a.X || a.ldx % 4 || a.ldx < ((a.c_in + 3) & ~3) || !al16(a.X) || a.X == a.Y)
+        throw std::runtime_error("conv1d: an activation input must be 16-byte aligned rows of c_in columns, and not the output");
+    } else {
+      throw std::runtime_error("conv1d: mode 0 | 1 | 2");
+    }
+    int tt, per_tap;
+    if (!conv1d_plan(a, tt, per_tap)) throw std::runtime_error("conv1d: tt = 64 does not fit this many input channels");
+    if ((int64_t)a.n_rows * ((a.T + tt - 1) / tt) > 0x7fffffff) throw std::runtime_error("conv1d: too many rows");
+    launch_or_record([a](hipStream_t st) { launch_conv1d(a, st); }, s, "conv1d");
+  });
+  m.def("seq_pool", [](py::dict d, uintptr_t s) {
+    SeqPoolArgs a{};
+    a.X = ptr<const float*>(d, "X");
+    a.Y = ptr<void*>(d, "Y");
+    a.m_ptr = ptr<const int32_t*>(d, "m_ptr");
+    a.n_rows = geti(d, "n_rows");
+    a.T = geti(d, "T");
+    a.C = geti(d, "C");
+    a.ldx = geti(d, "ldx");
+    a.ldy = geti(d, "ldy");
+    a.op = geti(d, "op");
+    a.y_bf16 = geti(d, "y_bf16");
+    if (!a.X || !a.Y) throw std::runtime_error("seq_pool: missing pointers");
+    if (a.n_rows < 0 || a.T < 1 || a.T > CONV_MAX_T || a.C < 1 || a.C > CONV_MAX_C || a.ldx < a.C || a.ldy < a.C)
+      throw std::runtime_error("seq_pool: sizes (1 <= T <= 1024, 1 <= C <= 256, ldx >= C, ldy >= C)");
+    if (a.op < POOL_LAST || a.op > POOL_SUM) throw std::runtime_error("seq_pool: op");
+    launch_or_record([a](hipStream_t st) { launch_seq_pool(a, st); }, s, "seq_pool");
+  });
   m.def("join", [](py::dict d, uintptr_t s) {
     JoinArgs a{};
     a.A = ptr<const void*>(d, "A");

@@ -283,6 +283,49 @@ struct SvmArgs {
 void launch_svm(const SvmArgs& a, hipStream_t st);
 int svm_tile(int M);  // rows per workgroup launch_svm picks (16 | 32 | 64)
 
+// ---- temporal convolutions (conv1d.hip): one layer of a Conv1D / TCN sequence model per launch,
+//   out[row][t][o] = act_post(act(b[o] + sum_j sum_c W[o][c][j] x[row][t - pad_left + j dil][c]) + res[row][t][o])
+// on v_mfma_f32_16x16x4_f32, f32 throughout; x is zero outside [0, T). Activation buffers are
+// channel-last [rows][T][ld] f32, ld a multiple of 4, 16-byte aligned.
+constexpr int CONV_MAX_C = 256;      // input / output channels
+constexpr int CONV_MAX_K = 8;        // taps
+constexpr int CONV_MAX_SPAN = 128;   // dil * (k - 1)
+constexpr int CONV_MAX_T = 1024;     // time steps
+struct ConvArgs {
+  // input: mode 0 dense X f32 [T][x_rows][c_in]; mode 1 per-account event ring (bf16 [C][ev_ring][I],
+  // c_in <= I, the seq_src rules of seq_input.h); mode 2 an activation buffer X [rows][T][ldx]
+  int32_t mode;
+  const float* X;
+  int32_t x_rows, ldx;
+  const uint16_t* ev;
+  const AcctRT* rt;
+  const int32_t* slots;     // [rows] (-1 -> all zeros)
+  int32_t ev_ring, I;
+  const float* W;           // fragment-packed [ceil(c_out / 16)][k][ceil(c_in / 16)][64 lanes][4] (plan.conv_tables)
+  const float* bias;        // [round_up(c_out, 16)], zeros past c_out
+  const float* res;         // [rows][T][ldr] added after act (nullable)
+  float* Y;                 // [rows][T][ldy]; columns [c_out, min(ldy, round_up(c_out, 16))) are written as zeros
+  int32_t ldr, ldy;
+  const int32_t* m_ptr;     // live rows in device memory (nullable -> n_rows)
+  int32_t n_rows, T, c_in, c_out, k, dil, pad_left;
+  int32_t act, act_post;    // GemmArgs::act codes
+  int32_t tt;               // time steps per workgroup: 0 auto | 32 | 64 (a row's result does not depend on it)
+  int32_t per_tap;          // 1: stage each tap's steps on their own (0: when tile + halo fit the LDS)
+};
+bool conv1d_plan(const ConvArgs& a, int& tt, int& per_tap);   // the tile launch_conv1d picks; false: no tile fits
+void launch_conv1d(const ConvArgs& a, hipStream_t st);
+
+enum SeqPoolOp : int32_t { POOL_LAST = 0, POOL_MEAN = 1, POOL_MAX = 2, POOL_SUM = 3 };
+struct SeqPoolArgs {
+  const float* X;           // [rows][T][ldx]
+  void* Y;                  // [rows][ldy] f32 or bf16, columns [0, C)
+  const int32_t* m_ptr;
+  int32_t n_rows, T, C, ldx, ldy;
+  int32_t op;               // SeqPoolOp; max: a NaN in the column gives NaN
+  int32_t y_bf16;
+};
+void launch_seq_pool(const SeqPoolArgs& a, hipStream_t st);
+
 // DAG join of two branches (join.hip): op 0 Y = A + B (na columns), op 1 Y = [A | B]
 struct JoinArgs {
   const void* A;

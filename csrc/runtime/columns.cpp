@@ -100,6 +100,22 @@ Tensor gather(const Node& n, const Tensor& x, const Tensor* idx_t, bool idx_cons
   const char* op = "Gather";
   const auto& raw = int_const(op, "indices", idx_t, idx_const);
   const int64_t axis = n.geti("axis", 0);
+  if (x.dims.size() == 3 && (axis == 2 || axis == -1)) {
+    // the last axis of a rank-3 value (a sequence model's [N][C][T]): 1-D indices give [N][C][k], a scalar [N][C]
+    if (idx_t->dims.size() > 1) fail(op, "indices must be a scalar or 1-D");
+    int64_t R, C;
+    rows_cols(op, x, R, C);
+    std::vector<int64_t> idx = raw;
+    for (auto& j : idx) {
+      if (j < -C || j >= C) fail(op, "index " + std::to_string(j) + " outside [-" + std::to_string(C) + ", " + std::to_string(C) + ")");
+      if (j < 0) j += C;
+    }
+    if (idx_t->dims.empty()) {
+      if (idx.size() != 1) fail(op, "a scalar index tensor must hold one value");
+      return take_columns(x, R, C, idx, {x.dims[0], x.dims[1]});
+    }
+    return take_columns(x, R, C, idx, {x.dims[0], x.dims[1], int64_t(idx.size())});
+  }
   if (x.dims.size() != 2 || (axis != 1 && axis != -1))
     fail(op, "only axis 1 / -1 of a 2-D value is supported (axis " + std::to_string(axis) + ", rank " +
                  std::to_string(x.dims.size()) + ")");

@@ -28,7 +28,8 @@ Tensor imputer(const Node& n, const Tensor& x);
 Tensor array_feature_extractor(const Node& n, const Tensor& x, const Tensor* y, bool y_const);
 
 // Gather along axis 1 / -1 of a 2-D value with constant int32 / int64 indices: 1-D indices give
-// [N][k], a scalar [N]. Negative indices wrap.
+// [N][k], a scalar [N]. Negative indices wrap. The last axis (2 / -1) of a rank-3 value [N][C][T] is
+// gathered the same way: [N][C][k], a scalar [N][C].
 Tensor gather(const Node& n, const Tensor& x, const Tensor* idx, bool idx_const);
 
 // Slice, opset >= 10 form (starts, ends, axes, steps as constants; any non-zero step; ONNX clamping).

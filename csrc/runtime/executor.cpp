@@ -9,6 +9,7 @@
 #include <stdexcept>
 
 #include "columns.h"
+#include "conv.h"
 
 namespace igp::exec {
 namespace {
@@ -870,6 +871,18 @@ std::map<std::string, Tensor> Executor::run(const std::map<std::string, Tensor>&
       bool cst = true;
       for (size_t i = 1; i < n.inputs.size(); ++i) cst &= n.inputs[i].empty() || g.initializers.count(n.inputs[i]) > 0;
       out = cols::slice(n, get(n.inputs[0]), opt(n, 1), opt(n, 2), opt(n, 3), opt(n, 4), cst);
+    } else if (op == "Conv") {
+      if (n.inputs.size() < 2) throw std::runtime_error("Conv: needs X and W");
+      out = conv::conv1d(n, get(n.inputs[0]), get(n.inputs[1]), g.initializers.count(n.inputs[1]) > 0, opt(n, 2));
+    } else if (op == "Pad") {
+      if (n.inputs.empty()) throw std::runtime_error("Pad: needs data");
+      bool cst = true;
+      for (size_t i = 1; i < n.inputs.size() && i < 3; ++i) cst &= n.inputs[i].empty() || g.initializers.count(n.inputs[i]) > 0;
+      out = conv::pad(n, get(n.inputs[0]), opt(n, 1), opt(n, 2), cst, opt(n, 3) != nullptr);
+    } else if (op == "GlobalAveragePool" || op == "GlobalMaxPool") {
+      out = conv::global_pool(op.c_str(), get(n.inputs.at(0)));
+    } else if (op == "ReduceMean" || op == "ReduceMax" || op == "ReduceSum") {
+      out = conv::reduce(n, get(n.inputs.at(0)), opt(n, 1), n.inputs.size() > 1 && g.initializers.count(n.inputs[1]) > 0);
     } else if (op == "FeatureVectorizer") {
       std::vector<const Tensor*> ts;
       for (auto& in : n.inputs) ts.push_back(&get(in));

@@ -107,6 +107,21 @@ def model_window(model, input_name: str, ring: int) -> int:
     return int(ring)
 
 
+def conv_model_feed(model, input_name: str, ring: int) -> dict:
+    """How the CPU path feeds an unmasked temporal-convolution model (one with Conv nodes), whose
+    graph fixes the sequence length: ``window``, the last steps of the right-aligned history it reads
+    (its own ``seq`` where that lies below the ring - what the device kernels read of the ring), and
+    ``batch_major`` for a layout-1 input [N, seq, in]. Empty for any other model."""
+    if not any(n["op_type"] == "Conv" for n in model.nodes()):
+        return {}
+    for name, _, dims, _ in model.inputs():
+        if name == input_name and len(dims) == 3:
+            major = int(dims[0]) <= 0 < int(dims[1])
+            seq = int(dims[1] if major else dims[0])
+            return dict(window=seq if 0 < seq < ring else int(ring), batch_major=major)
+    return {}
+
+
 class AbuseGpu:
     """K4 over the HBM event rings of one GPU shard. Requests carry only slots; one captured
     hipGraph per bucket: H2D [n | slots] -> fused 2-layer GRU + head (reads the rings) -> D2H."""
@@ -140,10 +155,10 @@ class AbuseGpu:
         # stream per pipeline slot (own device slab / output), so the next slot's batch runs
         # beside a batch-parallel launch that leaves CUs free (the 32-row split GRU fills 128 of
         # 256 CUs at 4096 rows). The weight-stationary cluster kernel needs the whole chip
-        # co-resident and a bidirectional model shares its intermediates: both stay on one
+        # co-resident and a bidirectional model or a TCN shares its intermediates: both stay on one
         # stream, as does a serving rank (its streams are budgeted to the 4 hardware queues,
         # engine/dp.py).
-        multi = overlap and not self.gp.ws_ok and not self.gm.bidirectional and depth > 1
+        multi = overlap and not self.gp.ws_ok and not self.gm.shares_intermediates and depth > 1
         if multi:
             # the split cluster kernel (gru_wsx) keeps one workspace per pack (counters, hand-off
             # slab, head partials): launches on several streams at once would share it (ADVICE
@@ -278,10 +293,12 @@ class AbuseGpu:
 class AbuseService:
     def __init__(self, engine, threshold: float = 0.7, gpu: Optional[List[AbuseGpu]] = None, executor=None,
                  input_name: str = "input", output_name: str = "output", group=None, group_model: bool = False,
-                 lens_input: Optional[str] = None, window: Optional[int] = None):
+                 lens_input: Optional[str] = None, window: Optional[int] = None, batch_major: bool = False):
         """``lens_input``: the executor model's sequence_lens graph input (None: an unmasked model, fed
-        zero-padded histories); ``window``: the steps such a model is fed (:func:`model_window`)."""
-        self.lens_input, self.window = lens_input, window
+        zero-padded histories); ``window``: the steps such a model is fed (:func:`model_window`; for an
+        unmasked temporal-convolution model the last ``window`` steps, :func:`conv_model_feed`);
+        ``batch_major``: the executor model's input is [N, seq, in]."""
+        self.lens_input, self.window, self.batch_major = lens_input, window, batch_major
         self.engine = engine
         self.group = group              # SPMD: the GRU runs on the rank that owns the account
         self.group_model = group_model
@@ -311,6 +328,10 @@ class AbuseService:
                 return np.asarray(y.get(self.output_name, list(y.values())[-1]), np.float32).reshape(-1)
             X = np.stack([be.event_history(int(s)) if s >= 0 else np.zeros_like(be.event_history(0))
                           for s in slots], axis=1)
+            if self.window and self.window < X.shape[0]:
+                X = X[-self.window:]
+            if self.batch_major:
+                X = np.ascontiguousarray(X.transpose(1, 0, 2))
             y = self.executor.run({self.input_name: X.astype(np.float32)})
             return np.asarray(y.get(self.output_name, list(y.values())[-1]), np.float32).reshape(-1)
         return None

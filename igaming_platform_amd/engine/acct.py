@@ -162,9 +162,9 @@ class AbuseNativeDevice:
         width = sc.width
         self.stream = torch.cuda.Stream(device=dev, priority=priority)
         # one stream per slot: a few hundred rows of 100-step GRU fill a few dozen CUs, so the
-        # slots' steps run side by side (a bidirectional model shares the pack's direction
-        # buffers between slots and keeps one stream)
-        shared = self.gm is not None and self.gm.bidirectional
+        # slots' steps run side by side (a model that shares intermediates between runs - a
+        # bidirectional layer's direction buffers, a TCN's activation buffers - keeps one stream)
+        shared = self.gm is not None and self.gm.shares_intermediates
         self.streams = [self.stream] if shared else [self.stream] + [
             torch.cuda.Stream(device=dev, priority=priority) for _ in range(self.depth - 1)]
         self.bufs = [dict(slab=torch.zeros(nb, dtype=torch.uint8, device=dev),
@@ -322,10 +322,24 @@ def attach_models(acct: NativeAcct, cfg, backend, ltv=None, owner: int = 0, abus
                                       max_batch=int(cfg.abuse.max_batch),
                                       priority=-100 if cfg.abuse.high_priority else 0,
                                       cluster_kernel=bool(cfg.abuse.cluster_kernel)), cfg)
+    elif backend.kind == "cpu" and hasattr(backend, "sc") and abuse_model is not None and not cpu_abuse_native_ok(
+            abuse_model, cfg.abuse_model.input_name, int(cfg.features.event_ring)):
+        # the C++ device feeds every unmasked model the whole ring in layout 0; such a model is
+        # answered by the Python path (AbuseService), which feeds it its own window and layout
+        log.warning("abuse model reads a window below the event ring or a batch-major input: CheckBonusAbuse stays "
+                    "on the Python path")
     elif backend.kind == "cpu" and hasattr(backend, "sc"):
         acct.attach(cpu_abuse_device(backend, abuse_model, max(cfg.gpu.buckets),
                                      cfg.abuse_model.input_name, cfg.abuse_model.output_name, depth), cfg)
     acct.set_abuse(cfg.scoring, cfg.abuse.threshold, cfg.abuse.link_wait_us)
+
+
+def cpu_abuse_native_ok(model, input_name: str, ring: int) -> bool:
+    """Whether the C++ CPU abuse device feeds ``model`` what the Python path and the GPU feed it: always,
+    except for a temporal-convolution model whose graph fixes a window below the ring or a batch-major input."""
+    from .abuse import conv_model_feed
+    feed = conv_model_feed(model, input_name, ring)
+    return not feed or (feed["window"] == ring and not feed["batch_major"])
 
 
 def abuse_device_plan(cfg, abuse_model, device) -> Optional[object]:

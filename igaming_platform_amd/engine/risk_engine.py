@@ -53,13 +53,16 @@ def _load_onnx(src):
 
 
 def _abuse_lens(am, cfg) -> dict:
-    """AbuseService arguments for an executor-run abuse model that reads ONNX sequence_lens."""
+    """AbuseService arguments for an executor-run abuse model that reads ONNX sequence_lens, or for a
+    temporal-convolution model (the window and layout its graph fixes)."""
     if am is None:
         return {}
     from ..models.plan import sequence_lens_input
-    from .abuse import model_window
+    from .abuse import conv_model_feed, model_window
     name = sequence_lens_input(am)
-    return dict(lens_input=name, window=model_window(am, "input", cfg.features.event_ring)) if name else {}
+    if name:
+        return dict(lens_input=name, window=model_window(am, "input", cfg.features.event_ring))
+    return conv_model_feed(am, "input", cfg.features.event_ring)
 
 
 class RiskEngine:

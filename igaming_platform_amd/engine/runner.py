@@ -79,6 +79,13 @@ class GruModel:
         return self.head is not None
 
     @property
+    def shares_intermediates(self) -> bool:
+        """Whether two ``run`` calls in flight at once would write the same device buffers (the
+        direction buffers of a bidirectional layer): the abuse runners then keep every pipeline slot
+        on one stream."""
+        return self.bidirectional
+
+    @property
     def masked(self) -> bool:
         return self.packs[0].masked
 
@@ -119,8 +126,115 @@ class LstmModel(GruModel):
     launch = staticmethod(K.lstm)
 
 
+class _NoClusterPack:
+    """What the abuse runners ask of a recurrent weight pack, for a model that has none: no
+    weight-stationary cluster path to disable, no split tile to size."""
+    ws_ok = wsx_ok = False
+    x3_rows = 16    # ignored
+
+    def disable_ws(self, keep_wsx: bool = False) -> None:
+        pass
+
+
+class TcnModel:
+    """A temporal-convolution plan on the device (csrc/kernels/conv1d.hip): one ``conv1d`` launch per
+    ConvStep, the ``seq_pool`` read-out, then the trailing dense layers (the N=1 head included) as
+    ``dense`` launches. f32 convolutions whatever the plan's precision. The interface is
+    :class:`GruModel`'s: dense X f32 [T, rows, I] or the store's event rings for ``slots`` (each
+    account's last min(ev_count, T) events right-aligned, zeros before them).
+
+    Activations are channel-last [rows, T, C_pad] f32 buffers: one per live value, shared between the
+    steps whose outputs are never live together (two ping-pong buffers for a plain stack; a residual
+    source keeps its buffer until its last reader has run)."""
+
+    bidirectional = False
+    split = False
+    masked = False
+    # one set of activation buffers: two runs in flight would overwrite each other's layers, so the
+    # abuse runners keep their pipeline slots on one stream (as for a bidirectional GRU)
+    shares_intermediates = True
+
+    def __init__(self, steps, device, split: bool, bmax: int):
+        kinds = [s.kind for s in steps]
+        if "seqpool" not in kinds:
+            raise ValueError("a temporal-convolution model needs a read-out (seqpool) step")
+        p = kinds.index("seqpool")
+        if p == 0 or any(k != "conv" for k in kinds[:p]):
+            raise ValueError("a temporal-convolution model must be convolution layers followed by one read-out")
+        if any(k != "dense" for k in kinds[p + 1:]):
+            bad = next(k for k in kinds[p + 1:] if k != "dense")
+            raise ValueError(f"a temporal-convolution model runs only dense layers behind its read-out, not {bad!r}")
+        for i in range(p + 1, len(steps)):
+            if step_inputs(steps, i) != (i - 1,):
+                raise ValueError("the layers behind the read-out must form a chain")
+        self.steps, self.n_conv, self.device = list(steps), p, device
+        self.seq = steps[0].seq
+        self.packs = [_NoClusterPack()]
+        last = steps[-1]
+        self.head = last if last.kind == "dense" and last.n == 1 else None
+        # the last step reading each conv output; a buffer is free again after it
+        last_read = {}
+        for i in range(p + 1):
+            for j in step_inputs(steps, i):
+                last_read[j] = i
+        T = max(int(self.seq), 1)
+        self.bufs: List[torch.Tensor] = []
+        self.buf_of: List[int] = []
+        width = -(-max(s.c_out for s in steps[:p]) // 4) * 4
+        holder: List[int] = []   # per buffer, the step whose output it holds
+        for i in range(p):
+            # a buffer is free once its value's last reader ran before this step (so never an input of step i)
+            b = next((b for b, j in enumerate(holder) if last_read.get(j, -1) < i), None)
+            if b is None:
+                self.bufs.append(torch.zeros((bmax, T, width), dtype=torch.float32, device=device))
+                holder.append(i)
+                b = len(self.bufs) - 1
+            holder[b] = i
+            self.buf_of.append(b)
+        self.T_alloc = T
+        pool = steps[p]
+        self.pooled = torch.zeros((bmax, pool.width), dtype=torch.float32, device=device)
+        self.mid = [torch.zeros((bmax, s.n), dtype=torch.float32, device=device) for s in steps[p + 1:-1]]
+
+    @property
+    def has_head(self) -> bool:
+        return self.head is not None
+
+    def run(self, n_rows: int, T: int, out: torch.Tensor, X: Optional[torch.Tensor] = None, store=None,
+            slots: Optional[torch.Tensor] = None, m_ptr: Optional[torch.Tensor] = None,
+            lens: Optional[torch.Tensor] = None) -> None:
+        """``out``: [rows] probabilities with an N=1 head, else [rows, width] of the last step."""
+        if lens is not None:
+            raise ValueError("a temporal-convolution model takes no sequence lengths")
+        if T != self.T_alloc:
+            raise ValueError(f"the model runs {self.T_alloc} time steps, not {T}")
+        steps, p = self.steps, self.n_conv
+        for i in range(p):
+            s = steps[i]
+            src = step_inputs(steps, i)[0]
+            Y = self.bufs[self.buf_of[i]]
+            res = None if s.res is None else self.bufs[self.buf_of[s.res]]
+            if src < 0:
+                K.conv1d(s, n_rows, T, Y, X=X, store=store, slots=slots, res=res, m_ptr=m_ptr)
+            else:
+                K.conv1d(s, n_rows, T, Y, A=self.bufs[self.buf_of[src]], res=res, m_ptr=m_ptr)
+        pool = steps[p]
+        tail = steps[p + 1:]
+        out2 = out.view(-1, 1) if out.dim() == 1 else out
+        src_buf = self.bufs[self.buf_of[step_inputs(steps, p)[0]]]
+        K.seq_pool(pool.op, src_buf, self.pooled if tail else out2, n_rows, T, pool.width, m_ptr=m_ptr)
+        cur = self.pooled
+        for j, s in enumerate(tail):
+            dst = out2 if j == len(tail) - 1 else self.mid[j]
+            K.dense(cur, s.w, s.b, dst, n_rows, s.n, s.k, act=s.act, m_ptr=m_ptr)
+            cur = dst
+
+
 def sequence_model(steps, device, split: bool, bmax: int):
-    """The device runner of a sequence plan's recurrent layers (+ head): GRU or LSTM."""
+    """The device runner of a sequence plan: GRU or LSTM layers (+ head), or a temporal-convolution
+    network (convolution layers, read-out, dense layers)."""
+    if steps and steps[0].kind == "conv":
+        return TcnModel(steps, device, split, bmax)
     if steps and steps[0].kind == "lstm":
         return LstmModel(steps, device, split, bmax)
     return GruModel(steps, device, split, bmax)
@@ -148,7 +262,10 @@ class DeviceModel:
             dt = (torch.bfloat16 if (s.kind in ("dense", "qdense", "dequant", "gru", "lstm", "join", "row", "cols")
                                      and feeds_mma and plan.precision == "bf16")
                   else torch.float32)
-            if step_qtype(s) is not None:
+            if s.kind in ("conv", "seqpool") and not last:
+                # TcnModel owns these steps' buffers; a placeholder keeps step_out indexed by step
+                self.step_out.append(torch.zeros((0, s.out_width), dtype=torch.float32, device=self.device))
+            elif step_qtype(s) is not None:
                 # quantised bytes: rows padded to 16 so qgemm loads and stores them as 16-byte vectors
                 self.step_out.append(torch.zeros((B, -(-s.out_width // 16) * 16), dtype=torch.int8, device=self.device))
             else:

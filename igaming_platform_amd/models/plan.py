@@ -63,6 +63,20 @@ steps:
                  starts a fresh one, so float arithmetic is never reordered and the step is
                  bit-equal to the executor. Up to 256 base columns and 4096 assembled ones; string
                  categories, ``zeros = 0`` and the int64 Imputer attributes raise :class:`PlanError`.
+* ``ConvStep`` / ``SeqPoolStep``  temporal-convolution (Conv1D / TCN) sequence models: the 3-D model input goes
+                 through ``Transpose`` (perm [1, 2, 0] for layout 0, [0, 2, 1] for layout 1) into a *sequence
+                 value*, logically [N, C, T]. Each ONNX ``Conv`` (1-D, stride 1, group 1, constant W) on one
+                 becomes a ``ConvStep`` of output length T -> ``conv1d`` (csrc/kernels/conv1d.hip, f32 whatever
+                 ``precision`` says); ``pads``, ``auto_pad``, a constant-zero ``Pad`` in front and a ``Slice`` (step
+                 1) behind compose into its ``pad_left``. A following Relu / Sigmoid / Tanh, a residual ``Add``
+                 with another sequence value (then the activation behind it) and an inference
+                 BatchNormalization fold into the step, under the exclusivity rule of the dense folds; Dropout /
+                 Identity fold away. GlobalAveragePool / GlobalMaxPool, Reduce{Mean,Max,Sum} over axis 2,
+                 Gather(axis 2, last index) and Slice[T - 1 : T] give the ``SeqPoolStep`` read-out (``seq_pool``),
+                 after which the value is an ordinary [N, C] one: dense layers follow. Limits ``CONV_MAX_C`` = 256
+                 channels, ``CONV_MAX_K`` = 8 taps, ``CONV_MAX_SPAN`` = 128 = dil (k - 1), ``CONV_MAX_T`` = 1024
+                 steps. Any other operator on a sequence value, a length other than T, a non-zero pad value,
+                 padding on N or C, a strided cut, GRU / LSTM layers in the same model raise :class:`PlanError`.
 * ``BatchNormalization`` (inference) is a per-column affine and folds like ``Scaler``;
   ``Dropout`` is folded away.
 * ai.onnx.ml ``LinearClassifier`` / ``LinearRegressor`` (post NONE / LOGISTIC; a two-class
@@ -262,7 +276,8 @@ class LSTMStep:
                         reverse=True, layout=self.layout, masked=self.masked)
 
 
-SEQUENCE_KINDS = ("gru", "lstm")   # recurrent steps: the plan is then a sequence model
+SEQUENCE_KINDS = ("gru", "lstm", "conv")   # recurrent / convolution steps: the plan is then a sequence model
+RECURRENT_KINDS = ("gru", "lstm")
 
 
 def is_sequence_step(s) -> bool:
@@ -270,7 +285,8 @@ def is_sequence_step(s) -> bool:
 
 
 def has_sequence(steps) -> bool:
-    """Whether the steps form a sequence model (GRU / LSTM layers: [T, rows, I] input, K4)."""
+    """Whether the steps form a sequence model (GRU / LSTM layers, K4, or the convolution layers of
+    a TCN: [T, rows, I] input)."""
     return any(is_sequence_step(s) for s in steps or ())
 
 
@@ -321,6 +337,10 @@ class Plan:
                 parts.append(f"svm({s.in_dim},{s.n_sv},{s.kernel})")
             elif s.kind == "cols":
                 parts.append(f"cols({s.in_width}->{s.out_width})")
+            elif s.kind == "conv":
+                parts.append(f"conv({s.c_in}->{s.c_out},k={s.k},d={s.dil},p={s.pad_left})")
+            elif s.kind == "seqpool":
+                parts.append(f"seqpool({s.op},{s.width})")
             else:
                 parts.append(f"{s.kind}(I={s.in_dim},H={s.hidden}{',lens' if getattr(s, 'masked', False) else ''})")
         return " -> ".join(parts)
@@ -547,6 +567,102 @@ def validate_svm(s: SVMStep) -> None:
         raise PlanError("svm: non-finite parameters")
 
 
+CONV_MAX_C = 256         # input / output channels of a ConvStep (csrc/kernels/launch.h CONV_MAX_C)
+CONV_MAX_K = 8           # taps
+CONV_MAX_SPAN = 128      # dil * (k - 1): the halo a time tile stages
+CONV_MAX_T = 1024        # time steps
+POOL_OPS = {"last": 0, "mean": 1, "max": 2, "sum": 3}   # csrc/kernels/launch.h SeqPoolOp
+
+
+@dataclass
+class ConvStep:
+    """One 1-D convolution layer of a temporal-convolution (TCN) sequence model on a sequence value,
+    logically [N, C, T] (csrc/kernels/conv1d.hip), f32 whatever the plan's precision. The output
+    length is always T:
+
+        out[o, t] = b[o] + sum_j sum_c W[o, c, j] * x[c, t - pad_left + j * dil]     (zero outside [0, T))
+
+    then ``act``, then ``+ res`` (the output of step ``res``, a sequence value of c_out channels; None:
+    nothing is added; the model input, -1, is not allowed), then ``act_post``."""
+    c_in: int
+    c_out: int
+    k: int
+    dil: int
+    pad_left: int
+    w_np: np.ndarray          # [C_out, k, C_in] f32
+    b_np: np.ndarray          # [C_out] f32
+    act: str = "none"
+    res: Optional[int] = None
+    act_post: str = "none"
+    seq: int = 0
+    layout: int = 0           # of the model input: 0 [T, N, I], 1 [N, T, I]
+    w: Any = None             # device tables (conv_tables)
+    b: Any = None
+    kind: str = "conv"
+    src: Optional[int] = None
+
+    @property
+    def out_width(self) -> int:
+        return self.c_out
+
+
+@dataclass
+class SeqPoolStep:
+    """The read-out of a sequence value [N, C, T] -> [N, C] (``seq_pool`` of conv1d.hip): ``last``
+    (step T - 1), ``mean`` / ``sum`` / ``max`` over t ascending; a NaN in the column makes ``max`` NaN."""
+    op: str
+    width: int
+    seq: int = 0
+    layout: int = 0
+    kind: str = "seqpool"
+    src: Optional[int] = None
+
+    @property
+    def out_width(self) -> int:
+        return self.width
+
+
+def check_conv(s: ConvStep) -> None:
+    """Host check of a convolution layer against what conv1d.hip is built for."""
+    if not (1 <= s.c_in <= CONV_MAX_C and 1 <= s.c_out <= CONV_MAX_C):
+        raise PlanError(f"conv: {s.c_in} -> {s.c_out} channels (the device kernel takes 1 .. {CONV_MAX_C})")
+    if not 1 <= s.k <= CONV_MAX_K:
+        raise PlanError(f"conv: kernel size {s.k} (the device kernel takes 1 .. {CONV_MAX_K})")
+    if s.dil < 1 or s.dil * (s.k - 1) > CONV_MAX_SPAN:
+        raise PlanError(f"conv: dilation {s.dil} x (k - 1) = {s.dil * (s.k - 1)} (the device kernel takes up to {CONV_MAX_SPAN})")
+    if not 1 <= s.seq <= CONV_MAX_T:
+        raise PlanError(f"conv: {s.seq} time steps (the device kernel takes 1 .. {CONV_MAX_T})")
+    if not 0 <= s.pad_left <= s.dil * (s.k - 1):
+        raise PlanError(f"conv: left padding {s.pad_left} outside [0, dil (k - 1) = {s.dil * (s.k - 1)}]")
+    if s.w_np.shape != (s.c_out, s.k, s.c_in) or s.b_np.shape != (s.c_out,):
+        raise PlanError("conv: weights must be [C_out, k, C_in] with one bias per output channel")
+    if s.act not in ACT_NAMES or s.act_post not in ACT_NAMES:
+        raise PlanError(f"conv: activation {s.act!r} / {s.act_post!r}")
+    if s.res is not None and s.res < 0:
+        raise PlanError("conv: the residual must be the output of a step (not the model input)")
+
+
+ACT_NAMES = ("none", "relu", "sigmoid", "tanh")
+
+
+def conv_tables(s: ConvStep) -> Dict[str, Any]:
+    """Host tables of a convolution layer, as torch tensors on the CPU (no GPU needed):
+
+    * ``w``    f32 [ceil(C_out / 16), k, ceil(C_in / 16), 64, 4] in MFMA fragment order: element
+      (ob, j, kc, lane, e) is W[ob * 16 + (lane & 15), kc * 16 + 4 * (lane >> 4) + e, j], zero past
+      C_out / C_in - one wave load of a fragment is 1 KiB contiguous;
+    * ``bias`` f32 [round_up(C_out, 16)], zeros past C_out."""
+    import torch
+    n_ob, n_kc = -(-s.c_out // 16), -(-s.c_in // 16)
+    wp = np.zeros((n_ob * 16, s.k, n_kc * 16), np.float32)
+    wp[:s.c_out, :, :s.c_in] = s.w_np
+    # [ob, li, j, kc, g, e] -> [ob, j, kc, g, li, e]; lane = 16 g + li
+    frag = wp.reshape(n_ob, 16, s.k, n_kc, 4, 4).transpose(0, 2, 3, 4, 1, 5)
+    bias = np.zeros(n_ob * 16, np.float32)
+    bias[:s.c_out] = s.b_np
+    return dict(w=torch.from_numpy(np.ascontiguousarray(frag).reshape(n_ob, s.k, n_kc, 64, 4)), bias=torch.from_numpy(bias))
+
+
 COL_MODES = {"pass": 0, "onehot": 1, "binarize": 2, "zero": 3}   # csrc/kernels/launch.h ColMode
 COL_IMPUTE, COL_IMP_NAN, COL_AFFINE = 0x10, 0x20, 0x40          # ... and the ColRecord flag bits
 COL_MAX_IN = 256         # widest base value the kernel stages (csrc/kernels/launch.h COL_MAX_IN)
@@ -685,7 +801,10 @@ def step_inputs(steps, i: int) -> Tuple[int, ...]:
     if s.kind == "join":
         return (s.a, s.b)
     src = getattr(s, "src", None)
-    return (i - 1 if src is None else src,)
+    src = i - 1 if src is None else src
+    if s.kind == "conv" and s.res is not None:
+        return (src, s.res)
+    return (src,)
 
 
 def step_consumers(steps) -> List[List[int]]:
@@ -724,6 +843,20 @@ class _Val:
     onehot3d: bool = False    # a OneHotEncoder output still shaped [N, C, n_cats] (Flatten / Reshape next)
     int_cast: bool = False    # behind a Cast to an integer type: only a OneHotEncoder reads it
     rank1: bool = False       # a Gather with a scalar index: [N]
+    pool3d: bool = False      # a pooled sequence value still shaped [N, C, 1] (Flatten / Squeeze / Reshape next)
+
+
+@dataclass
+class _Seq:
+    """A sequence value during lowering, logically [N, C, T]: the window [off, off + length) of the
+    output of ``step`` (-1: the transposed model input), which is zero outside [0, T). ``pending``: the
+    window of a convolution whose padding is still being composed (its Slice may follow)."""
+    step: int
+    C: int
+    off: int
+    length: int
+    pending: bool = False
+    exclusive: bool = True
 
 
 ALIAS_OPS = ("Identity", "Flatten", "Squeeze", "Unsqueeze", "Reshape", "ZipMap", "Cast", "Dropout")
@@ -869,6 +1002,9 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
             raise PlanError(f"{what}: a {cell}'s per-step outputs are lowered only into another {cell} layer")
         if v.quant is not None:
             raise PlanError(f"{what}: a quantised tensor is read only by DequantizeLinear")
+        if v.pool3d:
+            raise PlanError(f"{what}: a pooled sequence value [N, C, 1] must be flattened to [N, C] (Flatten / Squeeze / "
+                            "Reshape) before anything else reads it")
         if v.deq is not None:   # a reader other than a quantised Gemm: the DequantizeLinear runs on its own
             i = emit(DequantStep(v.width, *v.deq), v.step)
             v = vals[name] = _Val(i, v.width, ml_col=v.ml_col, cpu_col=v.cpu_col)
@@ -1020,10 +1156,272 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
             raise PlanError(f"{what}: {arr.size} values in {name} for {C} columns (1 or one per column)")
         return np.broadcast_to(arr, (C,))
 
+    # ---- sequence values of a temporal-convolution model: [N, C, T], entered through a Transpose of
+    # the 3-D model input; every operator on one is lowered in lower_seq below
+    seqs: Dict[str, _Seq] = {}
+    sq = dict(T=0, layout=0)
+
+    def ints_of(what, which, name):
+        if not name or name not in raw_inits or int(model.initializer_dtype(name)) not in (6, 7):
+            raise PlanError(f"{what}: {which} must be a constant integer tensor (an initializer)")
+        return [int(j) for j in np.asarray(model.initializer(name), np.int64).ravel()]
+
+    def seq_value(name) -> _Seq:
+        """The value as any reader but a Slice sees it: a convolution's composed padding is fixed now."""
+        v, T = seqs[name], sq["T"]
+        if v.pending:
+            st = steps[v.step]
+            span = st.dil * (st.k - 1)
+            if not v.exclusive:
+                raise PlanError("Conv: its padded output is cut by a Slice and also read elsewhere; one layer has one "
+                                "left padding, so several cuts of one convolution are not lowered")
+            if v.length != T:
+                raise PlanError(f"Conv: its padded and cut output has length {v.length}, not T = {T} "
+                                "(a convolution layer of a sequence model keeps the length)")
+            if not 0 <= -v.off <= span:
+                raise PlanError(f"Conv: pads and cuts compose to a left padding of {-v.off}, outside "
+                                f"[0, d (k - 1) = {span}]")
+            st.pad_left = -v.off
+            v = seqs[name] = replace(v, off=0, pending=False)
+        return v
+
+    def seq_full(name, what) -> _Seq:
+        v = seq_value(name)
+        if v.off != 0 or v.length != sq["T"]:
+            raise PlanError(f"{what}: reads a padded or cut sequence value (steps [{v.off}, {v.off + v.length}) of "
+                            f"T = {sq['T']}); only a Conv or a Slice may follow a Pad or a Slice")
+        return v
+
+    def seq_covers(v: _Seq, what):
+        if v.off > 0 or v.off + v.length < sq["T"]:
+            raise PlanError(f"{what}: reads a sequence value cut inside its T steps (steps [{v.off}, "
+                            f"{v.off + v.length}) of {sq['T']}): the cut is not lowered")
+
+    def seq_pool(opname, v, out_, what, keep3d):
+        if v.step < 0:
+            raise PlanError(f"{what}: a read-out of the model input itself is not lowered")
+        i = emit(SeqPoolStep(opname, v.C, seq=sq["T"], layout=sq["layout"]), v.step)
+        vals[out_] = _Val(i, v.C, pool3d=keep3d)
+
+    def lower_seq(n):
+        op, a, ins = n["op_type"], n["attrs"], n["inputs"]
+        x_, out_ = ins[0], n["outputs"][0]
+        T = sq["T"]
+        if x_ not in seqs and op != "Add":
+            raise PlanError(f"op {op} with a sequence value as a secondary input is not lowered")
+        if op == "Conv":
+            if any(s.kind in RECURRENT_KINDS for s in steps):
+                raise PlanError("Conv: GRU / LSTM layers and Conv mixed in one model are not lowered")
+            v = seq_value(x_)
+            seq_covers(v, op)
+            if len(ins) < 2 or ins[1] not in inits:
+                raise PlanError("Conv: W must be an initializer")
+            w = np.asarray(const(ins[1]), np.float32)
+            if w.ndim != 3:
+                raise PlanError(f"Conv: only 1-D convolutions are lowered (W [M, C, k]; this one has rank {w.ndim})")
+            M_, C_, k_ = (int(d_) for d_ in w.shape)
+            if int(a.get("group", 1)) != 1:
+                raise PlanError(f"Conv: group {int(a.get('group', 1))} is not lowered (1 only)")
+            ks = [int(j) for j in a.get("kernel_shape", [k_])]
+            dl = [int(j) for j in a.get("dilations", [1])]
+            sd = [int(j) for j in a.get("strides", [1])]
+            if ks != [k_] or len(dl) != 1 or len(sd) != 1:
+                raise PlanError(f"Conv: kernel_shape {ks} / dilations {dl} / strides {sd} do not describe W's 1-D kernel of {k_}")
+            if sd != [1]:
+                raise PlanError(f"Conv: stride {sd[0]} is not lowered (1 only)")
+            d_ = dl[0]
+            if d_ < 1 or k_ < 1:
+                raise PlanError("Conv: a dilation or kernel size of 0")
+            if C_ != v.C:
+                raise PlanError(f"Conv: W has {C_} input channels, the value {v.C}")
+            b = np.zeros(M_, np.float32)
+            if len(ins) > 2 and ins[2]:
+                if ins[2] not in inits:
+                    raise PlanError("Conv: B must be an initializer")
+                b = np.asarray(const(ins[2]), np.float32).ravel()
+                if b.size != M_:
+                    raise PlanError(f"Conv: B holds {b.size} values for {M_} output channels")
+            span = d_ * (k_ - 1)
+            ap = str(a.get("auto_pad", "NOTSET"))
+            if ap == "NOTSET":
+                pads = [int(j) for j in a.get("pads", [0, 0])]
+                if len(pads) != 2 or min(pads) < 0:
+                    raise PlanError(f"Conv: pads {pads} (two non-negative values [begin, end])")
+                cl, cr = pads
+            elif ap in ("SAME_UPPER", "SAME_LOWER"):
+                cl = span // 2 if ap == "SAME_UPPER" else span - span // 2
+                cr = span - cl
+            elif ap == "VALID":
+                cl = cr = 0
+            else:
+                raise PlanError(f"Conv: unknown auto_pad {ap!r}")
+            st = ConvStep(c_in=C_, c_out=M_, k=k_, dil=d_, pad_left=0, w_np=np.ascontiguousarray(w.transpose(0, 2, 1)),
+                          b_np=np.ascontiguousarray(b, np.float32), seq=T, layout=sq["layout"])
+            check_conv(st)   # the device limits (the padding is checked when it is fixed)
+            seqs[out_] = _Seq(emit(st, v.step), M_, v.off - cl, v.length + cl + cr - span, pending=True)
+        elif op == "Pad":
+            v = seq_value(x_)
+            seq_covers(v, op)
+            if str(a.get("mode", "constant")) != "constant":
+                raise PlanError(f"Pad: mode {a.get('mode')!r} is not lowered (constant only)")
+            if len(ins) > 3 and ins[3]:
+                raise PlanError("Pad: the axes input is not lowered")
+            if len(ins) > 1 and ins[1]:
+                pads = ints_of(op, "pads", ins[1])
+                val = 0.0
+                if len(ins) > 2 and ins[2]:
+                    if ins[2] not in inits:
+                        raise PlanError("Pad: the value must be a constant (an initializer)")
+                    val = float(np.asarray(const(ins[2]), np.float64).ravel()[0])
+            else:
+                pads, val = [int(j) for j in a.get("pads", [])], float(a.get("value", 0.0))
+            if len(pads) != 6 or min(pads) < 0:
+                raise PlanError(f"Pad: pads {pads} on a sequence value (six non-negative values)")
+            if val != 0.0:
+                raise PlanError(f"Pad: a non-zero pad value ({val:g}) on a sequence value is not lowered")
+            if pads[0] or pads[1] or pads[3] or pads[4]:
+                raise PlanError("Pad: padding on N or C of a sequence value is not lowered (the time axis only)")
+            seqs[out_] = replace(v, off=v.off - pads[2], length=v.length + pads[2] + pads[5],
+                                 exclusive=v.exclusive and single_use(x_))
+        elif op == "Slice":
+            if any(k_ in a for k_ in ("starts", "ends", "axes")):
+                raise PlanError("Slice: the attribute form (opset < 10) is not lowered")
+            v = seqs[x_]
+            starts = ints_of(op, "starts", ins[1] if len(ins) > 1 else "")
+            ends = ints_of(op, "ends", ins[2] if len(ins) > 2 else "")
+            axes = ints_of(op, "axes", ins[3]) if len(ins) > 3 and ins[3] else list(range(len(starts)))
+            stp = ints_of(op, "steps", ins[4]) if len(ins) > 4 and ins[4] else [1] * len(starts)
+            if not len(starts) == len(ends) == len(axes) == len(stp):
+                raise PlanError("Slice: starts, ends, axes and steps differ in length")
+            off, length, cut = v.off, v.length, False
+            for s_, e_, ax, st_ in zip(starts, ends, axes, stp):
+                ax += 3 if ax < 0 else 0
+                if ax not in (0, 1, 2):
+                    raise PlanError(f"Slice: axis {ax} of a sequence value [N, C, T]")
+                if st_ != 1:
+                    raise PlanError(f"Slice: a cut that is not contiguous (step {st_}) on a sequence value is not lowered")
+                if ax != 2:   # N is symbolic, C known: the explicit full range only
+                    if s_ != 0 or e_ < (2 ** 31 - 1 if ax == 0 else v.C):
+                        raise PlanError("Slice: only the time axis of a sequence value may be cut (N and C keep their "
+                                        "full range)")
+                    continue
+                if cut:
+                    raise PlanError("Slice: the time axis is named twice")
+                cut = True
+                s_, e_ = (s_ + length if s_ < 0 else s_), (e_ + length if e_ < 0 else e_)
+                s_, e_ = min(max(s_, 0), length), min(max(e_, 0), length)
+                if e_ <= s_:
+                    raise PlanError("Slice: an empty cut of a sequence value")
+                if (v.pending and 1 < T == length and (s_, e_) == (T - 1, T)
+                        and 0 <= -off <= steps[v.step].dil * (steps[v.step].k - 1)):
+                    # the last step of a convolution whose padding already composes (no activation in
+                    # between): a read-out, not part of the padding; the layer is fixed first
+                    v = seq_value(x_)
+                    off, length = v.off, v.length
+                off, length = off + s_, e_ - s_
+            seqs[out_] = replace(v, off=off, length=length, exclusive=v.exclusive and single_use(x_))
+        elif op in ACT_OPS:
+            v = seq_full(x_, op)
+            st = steps[v.step] if v.step >= 0 else None
+            ok = st is not None and st.kind == "conv" and v.exclusive and single_use(x_)
+            if ok and st.res is None and st.act == "none" and st.act_post == "none":
+                st.act = op.lower()
+            elif ok and st.act_post == "none":
+                st.act_post = op.lower()
+            else:
+                raise PlanError(f"{op}: an activation on a sequence value folds only into the convolution producing it "
+                                "(this value has several readers, is the model input, or both activation slots of "
+                                "the layer are taken)")
+            seqs[out_] = replace(v)
+        elif op == "Add":
+            if len(ins) != 2 or any(i not in seqs for i in ins):
+                raise PlanError("Add: on a sequence value only the sum of two sequence values (a residual connection) is lowered")
+            va, vb = seq_full(ins[0], op), seq_full(ins[1], op)
+            if va.C != vb.C:
+                raise PlanError(f"Add: sequence values of {va.C} and {vb.C} channels")
+            best = None
+            for v, name, o in ((va, ins[0], vb), (vb, ins[1], va)):
+                st = steps[v.step] if v.step >= 0 else None
+                if (st is not None and st.kind == "conv" and st.res is None and st.act_post == "none" and v.exclusive
+                        and single_use(name) and 0 <= o.step < v.step and (best is None or v.step > best[0].step)):
+                    best = (v, o)
+            if best is None:
+                raise PlanError("Add: a residual Add folds into a convolution whose output has no other reader; the "
+                                "other operand must be computed before it, by a step (not the model input)")
+            steps[best[0].step].res = best[1].step
+            seqs[out_] = _Seq(best[0].step, va.C, 0, T)
+        elif op == "BatchNormalization":
+            v = seqs[x_]
+            if int(a.get("training_mode", 0)):
+                raise PlanError("BatchNormalization: training_mode=1 is not lowered (inference only)")
+            if len(ins) < 5 or any(i not in inits for i in ins[1:5]):
+                raise PlanError("BatchNormalization: scale, B, mean and var must be initializers")
+            if any(o and o in reads for o in n["outputs"][1:]):
+                raise PlanError("BatchNormalization: the running statistics outputs are not lowered")
+            st = steps[v.step] if v.step >= 0 else None
+            if not (st is not None and st.kind == "conv" and st.act == "none" and st.res is None and st.act_post == "none"
+                    and v.exclusive and single_use(x_)):
+                raise PlanError("BatchNormalization: on a sequence value it folds only into the convolution producing "
+                                "it (before its activation, no other reader)")
+            g_, b_, mu, var = (np.asarray(const(i), np.float64).ravel() for i in ins[1:5])
+            if not g_.size == b_.size == mu.size == var.size == v.C:
+                raise PlanError(f"BatchNormalization: scale / B / mean / var must hold one value per channel ({v.C})")
+            sc = g_ / np.sqrt(var + float(a.get("epsilon", 1e-5)))
+            st.w_np = np.ascontiguousarray(st.w_np.astype(np.float64) * sc[:, None, None], np.float32)
+            st.b_np = (st.b_np.astype(np.float64) * sc + (b_ - mu * sc)).astype(np.float32)
+            seqs[out_] = replace(v)
+        elif op in ("Identity", "Dropout"):
+            if op == "Dropout":
+                if len(n["outputs"]) > 1 and n["outputs"][1] and n["outputs"][1] in reads:
+                    raise PlanError("Dropout: its mask output is read, which is not lowered")
+                if len(ins) > 2 and ins[2] in inits and np.asarray(const(ins[2])).ravel()[:1].any():
+                    raise PlanError("Dropout: training_mode is a constant true (inference only)")
+            seqs[out_] = seqs[x_]
+        elif op in ("GlobalAveragePool", "GlobalMaxPool"):
+            seq_pool("mean" if op == "GlobalAveragePool" else "max", seq_full(x_, op), out_, op, True)
+        elif op in ("ReduceMean", "ReduceMax", "ReduceSum"):
+            axes = (ints_of(op, "axes", ins[1]) if len(ins) > 1 and ins[1] else [int(j) for j in a.get("axes", [])])
+            if [ax + 3 if ax < 0 else ax for ax in axes] != [2]:
+                raise PlanError(f"{op}: on a sequence value only a reduction over the time axis (axis 2) alone is lowered")
+            seq_pool(op[6:].lower(), seq_full(x_, op), out_, op, bool(int(a.get("keepdims", 1))))
+        elif op == "Gather":
+            if int(a.get("axis", 0)) not in (2, -1):
+                raise PlanError(f"Gather: axis {int(a.get('axis', 0))} of a sequence value is not lowered (the time axis only)")
+            idx = ints_of(op, "the indices", ins[1] if len(ins) > 1 else "")
+            nd = np.asarray(model.initializer(ins[1])).ndim
+            if nd > 1 or len(idx) != 1 or idx[0] not in (-1, T - 1):
+                raise PlanError("Gather: on a sequence value only the last step (index -1 or T - 1) is lowered")
+            seq_pool("last", seq_full(x_, op), out_, op, nd == 1)
+        elif op in ("Squeeze", "Flatten", "Reshape"):
+            v = seq_value(x_)
+            if v.off != T - 1 or v.length != 1:
+                raise PlanError(f"{op}: on a sequence value it is lowered only behind a Slice of the last step ([T - 1 : T])")
+            seq_pool("last", v, out_, op, False)
+        else:
+            raise PlanError(f"op {op} is not lowered on a sequence value ([N, C, T]: Conv, Pad, Slice, Relu / Sigmoid / "
+                            "Tanh, a residual Add, BatchNormalization, Dropout, Identity and the read-outs are)")
+
     for n in order:
         op, a = n["op_type"], n["attrs"]
         ins = n["inputs"]
         x = ins[0] if ins else ""
+        if op == "Transpose" and x == input_name and seq_input and not seqs:
+            perm = [int(p) for p in a.get("perm", [])]
+            if perm in ([1, 2, 0], [0, 2, 1]):
+                lay = 0 if perm == [1, 2, 0] else 1
+                T_ = int(dims[1] if lay else dims[0])
+                if in_width <= 0 or T_ <= 0:
+                    raise PlanError("Transpose: a temporal-convolution model needs fixed seq and feature dimensions of its input")
+                if T_ > CONV_MAX_T:
+                    raise PlanError(f"conv: {T_} time steps (the device kernel takes 1 .. {CONV_MAX_T})")
+                sq["T"], sq["layout"] = T_, lay
+                seqs[n["outputs"][0]] = _Seq(-1, in_width, 0, T_)
+                continue
+        if any(i in seqs for i in ins):
+            lower_seq(n)
+            continue
+        if op in ("GRU", "LSTM") and any(s.kind in ("conv", "seqpool") for s in steps):
+            raise PlanError(f"{op}: GRU / LSTM layers and Conv mixed in one model are not lowered")
         if op in ("QLinearMatMul", "QLinearConv", "QLinearAdd", "QGemm", "MatMulInteger", "ConvInteger",
                   "DynamicQuantizeLinear"):
             raise PlanError(f"op {op} is not lowered to the device: {QDQ_ONLY}")
@@ -1501,6 +1899,8 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
                                     "[N, C * n_cats] (Flatten axis 1 / Reshape) before anything else reads it")
             elif v.cols is not None and v.rank1 and op in ("Unsqueeze", "Reshape", "Flatten"):
                 v = replace(v, rank1=False)   # [N] -> [N, 1]
+            elif v.pool3d and op in ("Flatten", "Squeeze", "Reshape"):
+                v = replace(v, pool3d=False)  # [N, C, 1] -> [N, C]
             vals[n["outputs"][0]] = v
             continue
         if op == "Transpose":
@@ -1705,8 +2105,11 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
             continue
         raise PlanError(f"op {op} is not lowered to the device")
 
+    if output_name in seqs:
+        raise PlanError("the output is a sequence value [N, C, T]: a read-out (last step, mean, max or sum over time) "
+                        "must follow")
     fv = vals.get(output_name)
-    if fv is None or fv.label or fv.quant is not None:
+    if fv is None or fv.label or fv.quant is not None or fv.pool3d:
         raise PlanError("the primary output must be a score / probability tensor")
     if fv.deq is not None or fv.cols is not None:
         # a trailing Q -> DQ: the DequantizeLinear is the last step; a column view: its ColumnStep
@@ -1719,17 +2122,30 @@ def compile_onnx(model, input_name: str = "input", output_name: str = "output",
         s = next(s for s in steps if s.kind == "row")
         raise PlanError(f"sequence models are lowered as chains (GRU / LSTM layers + head) only: a row step "
                         f"({s.act if s.op == 'act' else s.op}) in a sequence plan is not lowered")
-    if has_sequence(steps) and any(s.kind == "join" or s.src != i - 1 for i, s in enumerate(steps)):
+    convs = any(s.kind == "conv" for s in steps)
+    if not convs and has_sequence(steps) and any(s.kind == "join" or s.src != i - 1 for i, s in enumerate(steps)):
         raise PlanError("sequence models are lowered as chains (GRU / LSTM layers + head) only")
+    if convs:
+        kinds = [s.kind for s in steps]
+        p = kinds.index("seqpool") if "seqpool" in kinds else len(kinds)
+        if kinds.count("seqpool") != 1 or any(k != "conv" for k in kinds[:p]):
+            raise PlanError("a temporal-convolution model is lowered as convolution layers and one read-out")
+        for i, s in enumerate(steps[p + 1:], p + 1):
+            if s.kind != "dense" or s.src != i - 1:
+                raise PlanError(f"sequence models are lowered as convolution layers, a read-out and a chain of dense layers "
+                                f"only: a {s.kind} step behind the read-out is not lowered")
+        for s in steps[:p]:
+            check_conv(s)
     fam = model.metadata.get("family", "")
     if not fam:
         kinds = [s.kind for s in steps if s.kind != "cols"]   # a column front end keeps the estimator's family
         fam = ("svm" if kinds == ["svm"] else "gbdt" if kinds == ["tree"] else "stacked" if kinds and kinds[0] == "tree"
-               else "gru" if "gru" in kinds else "lstm" if "lstm" in kinds else "mlp")
+               else "gru" if "gru" in kinds else "lstm" if "lstm" in kinds else "tcn" if "conv" in kinds else "mlp")
     plan = Plan(family=fam, in_width=in_width, steps=steps, out_width=fv.width, ml_col=fv.ml_col,
                 metadata=dict(model.metadata), input_name=input_name, output_name=output_name,
                 seq_input=seq_input, cpu_col=fv.cpu_col, lens_input=lens_seen[0] if lens_seen else None)
-    return fuse(plan) if fuse_heads else fuse(plan, heads=False)
+    # (a TCN's trailing dense layers stay dense steps: runner.TcnModel runs them one by one)
+    return fuse(plan) if fuse_heads and not convs else fuse(plan, heads=False)
 
 
 def sequence_lens_input(model) -> Optional[str]:
@@ -1801,6 +2217,8 @@ def fuse(plan: Plan, heads: bool = True) -> Plan:
         else:
             src = remap[ins[oi][0]]
             s.src = None if src == j - 1 else src
+            if s.kind == "conv" and s.res is not None:
+                s.res = remap[s.res]
     plan.steps = out
     return plan
 
@@ -1937,6 +2355,10 @@ def to_device(plan: Plan, device, precision: str = "fp32") -> Plan:
             s.sv_norm = None if t["sv_norm"] is None else t["sv_norm"].to(device)
         elif s.kind == "cols":
             upload_columns(s, device)   # the host check, then the table
+        elif s.kind == "conv":
+            check_conv(s)   # before any upload
+            t = conv_tables(s)
+            s.w, s.b = t["w"].to(device), t["bias"].to(device)
         elif s.kind == "qdense":
             t = qdense_tables(s)
             s.w8, s.corr, s.mult, s.b = (t[k].to(device) for k in ("w8", "corr", "mult", "bias"))

@@ -14,6 +14,8 @@ names. Input name ``input`` / primary output ``output`` follow ``onnx_model.go:3
 * cfg4 ``ltv_mlp``:  input[N,256] -> (Gemm -> Relu) x4 (width 512) -> Gemm -> output[N,1]
 * cfg5 ``gru``:      input[T=100,N,16] -> GRU(256) -> Squeeze -> GRU(256) -> Y_h
                       -> Reshape[N,256] -> Gemm -> Sigmoid -> output[N,1]
+* ``tcn``:            input[T=100,N,16] -> Transpose[N,16,T] -> residual blocks of dilated causal Conv
+                      -> last step / mean / max over time -> Gemm -> Sigmoid -> output[N,1]
 """
 from __future__ import annotations
 
@@ -698,6 +700,103 @@ def columns(n_features: int = 30, n_trees: int = 20, depth: int = 4, seed: int =
     return model(nodes, ins, [value_info("output", S.FLOAT, ["N", 1])], inits, name="columns_gbdt", metadata=meta)
 
 
+def tcn(seq: int = 100, in_dim: int = 16, channels=(32, 32), kernel: int = 3, dilations=(1, 2), readout: str = "last",
+        layout: int = 0, causal: bool = True, style: str = "pads", residual: bool = True, head: bool = True,
+        seed: int = 13, readout_form: str = "default", batch_norm: bool = False, weights=None):
+    """Temporal convolutional network (Bai et al.): one residual block per entry of ``channels`` /
+    ``dilations``, each ``conv -> Relu -> conv -> Relu``, ``Add`` with the block input (through a k = 1
+    Conv where the channel count changes), ``Relu``; ``residual=False`` leaves the plain conv stack.
+
+    ``input`` is [seq, N, in_dim] (``layout`` 0) or [N, seq, in_dim] (1), as the GRU / LSTM builders'; a
+    Transpose makes it [N, C, T]. Causal padding is written in one of three ways (``style``): ``pads``
+    (the Conv attribute [d (k - 1), 0]), ``chomp`` (symmetric pads, then a Slice dropping the tail: the
+    PyTorch export) or ``pad_op`` (a Pad in front of an unpadded Conv); ``causal=False`` pads both sides
+    ("same"). ``readout``: ``last`` (Gather axis 2, index -1; ``readout_form="slice"``: Slice + Squeeze),
+    ``mean`` / ``max`` (GlobalAveragePool / GlobalMaxPool + Flatten; ``readout_form="reduce"``:
+    ReduceMean / ReduceMax over axis 2). Then Gemm -> Sigmoid -> [N, 1]; ``head=False``: the pooled
+    [N, C]. ``batch_norm`` puts an inference BatchNormalization behind every block convolution.
+    ``weights``: a callable (shape, rng) -> array replacing the random initialisation (integer test
+    models)."""
+    if len(channels) != len(dilations) or not channels:
+        raise ValueError("tcn: one dilation per block")
+    if style not in ("pads", "chomp", "pad_op") or readout not in ("last", "mean", "max"):
+        raise ValueError("tcn: style pads | chomp | pad_op, readout last | mean | max")
+    rng = np.random.default_rng(seed)
+    nodes, inits = [], []
+
+    def init(shape, fan):
+        if weights is not None:
+            return np.asarray(weights(shape, rng), np.float32).reshape(shape)
+        s = 1.0 / np.sqrt(fan)
+        return rng.uniform(-s, s, shape).astype(np.float32)
+
+    def const(name, arr, scalar=False):
+        t = tensor(name, np.asarray(arr))
+        if scalar:
+            del t.dims[:]
+        inits.append(t)
+        return name
+
+    def conv(tag, x, cin, cout, k, d, act=True):
+        span = d * (k - 1)
+        w, b = const(f"{tag}_W", init((cout, cin, k), cin * k)), const(f"{tag}_B", init((cout,), cin * k))
+        y = f"{tag}_y"
+        if not causal or span == 0:
+            nodes.append(node("Conv", [x, w, b], [y], kernel_shape=[k], dilations=[d], pads=[span // 2, span - span // 2]))
+        elif style == "pads":
+            nodes.append(node("Conv", [x, w, b], [y], kernel_shape=[k], dilations=[d], pads=[span, 0]))
+        elif style == "chomp":
+            nodes.append(node("Conv", [x, w, b], [f"{tag}_full"], kernel_shape=[k], dilations=[d], pads=[span, span]))
+            nodes.append(node("Slice", [f"{tag}_full", const(f"{tag}_s", np.array([0], np.int64)),
+                                        const(f"{tag}_e", np.array([-span], np.int64)),
+                                        const(f"{tag}_ax", np.array([2], np.int64))], [y]))
+        else:
+            nodes.append(node("Pad", [x, const(f"{tag}_p", np.array([0, 0, span, 0, 0, 0], np.int64))], [f"{tag}_pad"]))
+            nodes.append(node("Conv", [f"{tag}_pad", w, b], [y], kernel_shape=[k], dilations=[d], pads=[0, 0]))
+        if batch_norm and act:
+            for nm, arr in (("g", rng.uniform(0.5, 1.5, cout)), ("b", rng.uniform(-0.2, 0.2, cout)),
+                            ("m", rng.uniform(-0.2, 0.2, cout)), ("v", rng.uniform(0.5, 1.5, cout))):
+                const(f"{tag}_bn_{nm}", arr.astype(np.float32))
+            nodes.append(node("BatchNormalization", [y] + [f"{tag}_bn_{nm}" for nm in "gbmv"], [f"{tag}_bn"], epsilon=1e-5))
+            y = f"{tag}_bn"
+        if act:
+            nodes.append(node("Relu", [y], [f"{tag}_a"]))
+            y = f"{tag}_a"
+        return y
+
+    nodes.append(node("Transpose", ["input"], ["x0"], perm=[0, 2, 1] if layout else [1, 2, 0]))
+    x, cin = "x0", in_dim
+    for bi, (cout, d) in enumerate(zip(channels, dilations)):
+        h = conv(f"b{bi}c1", x, cin, cout, kernel, d)
+        h = conv(f"b{bi}c2", h, cout, cout, kernel, d)
+        if residual:
+            skip = x if cin == cout else conv(f"b{bi}ds", x, cin, cout, 1, 1, act=False)
+            nodes += [node("Add", [h, skip], [f"b{bi}_sum"]), node("Relu", [f"b{bi}_sum"], [f"b{bi}_out"])]
+            h = f"b{bi}_out"
+        x, cin = h, cout
+    pooled = "pooled" if head else "output"
+    if readout == "last" and readout_form == "slice":
+        nodes += [node("Slice", [x, const("ro_s", np.array([-1], np.int64)), const("ro_e", np.array([2 ** 31 - 1], np.int64)),
+                                 const("ro_ax", np.array([2], np.int64))], ["ro3"]),
+                  node("Squeeze", ["ro3", const("ro_sq", np.array([2], np.int64))], [pooled])]
+    elif readout == "last":
+        nodes.append(node("Gather", [x, const("ro_idx", np.array([-1], np.int64), scalar=True)], [pooled], axis=2))
+    elif readout_form == "reduce":
+        nodes.append(node("ReduceMean" if readout == "mean" else "ReduceMax", [x], [pooled], axes=[2], keepdims=0))
+    else:
+        nodes += [node("GlobalAveragePool" if readout == "mean" else "GlobalMaxPool", [x], ["ro3"]),
+                  node("Flatten", ["ro3"], [pooled], axis=1)]
+    if head:
+        const("Wh", init((cin, 1), cin))
+        const("Bh", np.zeros(1, np.float32) if weights is None else init((1,), cin))
+        nodes += [node("Gemm", ["pooled", "Wh", "Bh"], ["logit"]), node("Sigmoid", ["logit"], ["output"])]
+    x_dims = ["N", seq, in_dim] if layout else [seq, "N", in_dim]
+    return model(nodes, [value_info("input", S.FLOAT, x_dims)], [value_info("output", S.FLOAT, ["N", 1 if head else cin])],
+                 inits, name="abuse_tcn",
+                 metadata={"family": "tcn", "seq": str(seq), "blocks": str(len(channels)), "kernel": str(kernel),
+                           "readout": readout, "layout": str(layout)})
+
+
 BUILDERS = {"qdq_mlp": qdq_mlp, "columns": columns,
             "logistic": logistic, "gbdt": gbdt, "gbdt_v5": gbdt_v5, "stacked": stacked, "ltv_mlp": ltv_mlp, "gru": gru,
             "lstm": lstm, "torch_mlp": torch_mlp, "tabular_resnet": tabular_resnet,
@@ -705,5 +804,10 @@ BUILDERS = {"qdq_mlp": qdq_mlp, "columns": columns,
             "mlp_classifier": mlp_classifier, "wide_deep": wide_deep, "residual_mlp": residual_mlp, "svm": svm}
 
 
+# sequence models whose graphs use Gather / Slice (BUILDERS lists the families that hold none of the
+# column operators, besides ``columns`` itself)
+SEQ_BUILDERS = {"tcn": tcn}
+
+
 def build(kind: str, **kw):
-    return BUILDERS[kind](**kw)
+    return (BUILDERS.get(kind) or SEQ_BUILDERS[kind])(**kw)

@@ -492,6 +492,100 @@ def svm(step, X: torch.Tensor, Y: torch.Tensor, M: int, m_ptr: Optional[torch.Te
     _mod().svm(d, _stream())
 
 
+CONV_MAX_C, CONV_MAX_K, CONV_MAX_SPAN, CONV_MAX_T = 256, 8, 128, 1024   # csrc/kernels/launch.h
+POOL_OPS = {"last": 0, "mean": 1, "max": 2, "sum": 3}
+
+
+def _seq_buf(t: Optional[torch.Tensor], name: str, n_rows: int, T: int, C: int, dev) -> int:
+    """A channel-last activation buffer [rows >= n_rows, T, ld] float32, ld a multiple of 4 holding
+    C columns, 16-byte aligned."""
+    if t is None or t.dim() != 3 or t.dtype != torch.float32:
+        raise ValueError(f"{name}: must be a 3-D float32 tensor [rows, T, channels]")
+    if t.shape[0] < n_rows or t.shape[1] != T or t.shape[2] % 4 or t.shape[2] < C:
+        raise ValueError(f"{name}: shape {tuple(t.shape)} does not hold [{n_rows}, {T}, {C}] with the channels padded to a "
+                         "multiple of 4")
+    p = _need(t, name, torch.float32, device=dev)
+    if p % 16:
+        raise ValueError(f"{name}: must be 16-byte aligned")
+    return p
+
+
+def conv1d(step, n_rows: int, T: int, Y: torch.Tensor, X: Optional[torch.Tensor] = None, store=None,
+           slots: Optional[torch.Tensor] = None, A: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None,
+           m_ptr: Optional[torch.Tensor] = None, tt: int = 0, per_tap: bool = False) -> None:
+    """One convolution layer (conv1d.hip) of an uploaded models.plan.ConvStep, f32 whatever the plan's
+    precision: Y[:n_rows] ([rows, T, ld >= c_out] channel-last; the columns past c_out of the last
+    16-channel block are written as zeros) =
+    act_post(act(conv(input) + bias) + res). The input is one of: ``X`` the dense model input
+    [T, rows, c_in] float32; ``store`` + ``slots`` the store's event rings (the last min(ev_count, T)
+    events right-aligned, zeros before them and for slot -1); ``A`` an activation buffer
+    [rows, T, ld >= c_in]. ``res``: a buffer shaped like Y. ``tt`` (0 | 32 | 64 time steps per workgroup)
+    and ``per_tap`` force the tiling; a row's result does not depend on them."""
+    dev = Y.device
+    ci, co, k, dil = int(step.c_in), int(step.c_out), int(step.k), int(step.dil)
+    if not (1 <= ci <= CONV_MAX_C and 1 <= co <= CONV_MAX_C and 1 <= k <= CONV_MAX_K and dil >= 1
+            and dil * (k - 1) <= CONV_MAX_SPAN and 1 <= T <= CONV_MAX_T and n_rows >= 0):
+        raise ValueError(f"conv1d: channels <= {CONV_MAX_C}, k <= {CONV_MAX_K}, dil (k - 1) <= {CONV_MAX_SPAN}, "
+                         f"1 <= T <= {CONV_MAX_T}")
+    if not 0 <= int(step.pad_left) <= dil * (k - 1):
+        raise ValueError("conv1d: pad_left must lie in [0, dil (k - 1)]")
+    if step.act not in ACT or step.act_post not in ACT or tt not in (0, 32, 64):
+        raise ValueError("conv1d: activation / tt")
+    n_ob, n_kc = -(-co // 16), -(-ci // 16)
+    if tt == 64 and 64 * (n_kc * 16 + 4) > 16384:
+        raise ValueError("conv1d: tt = 64 does not fit this many input channels")
+    w, b = step.w, step.b
+    if w is None or b is None or w.dtype != torch.float32 or w.numel() != n_ob * k * n_kc * 256 or b.numel() != n_ob * 16:
+        raise ValueError("conv1d: the step's packed weights are not uploaded for these sizes (models.plan.conv_tables)")
+    if (res is not None) != (step.res is not None):
+        raise ValueError("conv1d: res must be given exactly when the step has a residual")
+    if sum(t is not None for t in (X, A, store)) != 1:
+        raise ValueError("conv1d: exactly one input: X, A or (store, slots)")
+    d = dict(W=_need(w, "W", torch.float32, device=dev), w_numel=int(w.numel()), bias=_need(b, "bias", torch.float32, device=dev),
+             Y=_seq_buf(Y, "Y", n_rows, T, co, dev), ldy=int(Y.shape[2]),
+             m_ptr=_opt(m_ptr, "m_ptr", dtype=torch.int32, min_numel=1, device=dev), n_rows=int(n_rows), T=int(T),
+             c_in=ci, c_out=co, k=k, dil=dil, pad_left=int(step.pad_left), act=ACT[step.act], act_post=ACT[step.act_post],
+             tt=int(tt), per_tap=int(bool(per_tap)))
+    if res is not None:
+        d.update(res=_seq_buf(res, "res", n_rows, T, co, dev), ldr=int(res.shape[2]))
+    if A is not None:
+        if A.data_ptr() == Y.data_ptr():
+            raise ValueError("conv1d: a layer cannot run in place (other time tiles still read the input)")
+        d.update(mode=2, X=_seq_buf(A, "A", n_rows, T, ci, dev), ldx=int(A.shape[2]))
+    elif X is not None:
+        if X.dim() != 3 or X.shape[0] != T or X.shape[1] < n_rows or X.shape[2] != ci:
+            raise ValueError(f"conv1d: X must be [{T}, rows >= {n_rows}, {ci}]")
+        d.update(mode=0, X=_need(X, "X", torch.float32, device=dev), x_rows=int(X.shape[1]))
+    else:
+        if slots is None or store.ev is None:
+            raise ValueError("conv1d: need X, A or (store with event rings, slots)")
+        if store.ev.shape[2] != ci or store.ev.shape[1] < T or ci % 4:
+            raise ValueError("conv1d: event ring width / length does not match the model")
+        d.update(mode=1, ev=_need(store.ev, "ev", torch.int16, device=dev), rt=_need(store.rt, "rt", torch.int32, device=dev),
+                 slots=_need(slots, "slots", torch.int32, n_rows, dev), ev_ring=int(store.ev.shape[1]), I=int(store.ev.shape[2]))
+    _mod().conv1d(d, _stream())
+
+
+def seq_pool(op: str, X: torch.Tensor, Y: torch.Tensor, n_rows: int, T: int, C: int,
+             m_ptr: Optional[torch.Tensor] = None) -> None:
+    """The read-out of a sequence value (conv1d.hip seq_pool): Y[:n_rows, :C] (float32 or bfloat16) =
+    ``op`` over the T steps of X [rows, T, ld >= C] float32: ``last`` copies step T - 1; ``mean``,
+    ``sum`` and ``max`` run over t ascending; a NaN in the column makes ``max`` NaN."""
+    dev = Y.device
+    if op not in POOL_OPS:
+        raise ValueError(f"seq_pool: op {op!r} (last | mean | max | sum)")
+    if not (1 <= T <= CONV_MAX_T and 1 <= C <= CONV_MAX_C and n_rows >= 0):
+        raise ValueError(f"seq_pool: 1 <= T <= {CONV_MAX_T}, 1 <= C <= {CONV_MAX_C}, rows >= 0")
+    if X.dim() != 3 or X.dtype != torch.float32 or X.shape[0] < n_rows or X.shape[1] != T or X.shape[2] < C:
+        raise ValueError(f"seq_pool: X must be float32 [rows >= {n_rows}, {T}, >= {C}]")
+    if Y.dim() != 2 or Y.dtype not in (torch.float32, torch.bfloat16) or Y.shape[0] < n_rows or Y.shape[1] < C:
+        raise ValueError(f"seq_pool: Y must be float32 or bfloat16 [rows >= {n_rows}, >= {C}]")
+    d = dict(X=_need(X, "X", torch.float32, device=dev), Y=_need(Y, "Y", device=dev),
+             m_ptr=_opt(m_ptr, "m_ptr", dtype=torch.int32, min_numel=1, device=dev), n_rows=int(n_rows), T=int(T), C=int(C),
+             ldx=int(X.shape[2]), ldy=int(Y.shape[1]), op=POOL_OPS[op], y_bf16=int(Y.dtype == torch.bfloat16))
+    _mod().seq_pool(d, _stream())
+
+
 COL_MAX_IN, COL_MAX_OUT, COL_RECORD_BYTES = 256, 4096, 32   # csrc/kernels/launch.h
 
 

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Per-kernel device time of one scoring step (events around each launch, interleaved rounds
-in one process). Usage: python tools/kbench.py [--config cfg3] [--rounds 50]"""
+in one process). Usage: python tools/kbench.py [--config cfg3] [--rounds 50]
+--config rowops: the row-op kernels alone; --config tcn: conv1d per layer, seq_pool and the head of a
+temporal-convolution model, the whole model, and the 2 x 256 GRU beside it."""
 import argparse
 import json
 import os
@@ -53,9 +55,70 @@ def rowops(rounds: int, out: str) -> None:
             json.dump(dict(config="rowops", kernels=res), f, indent=1)
 
 
+def tcn(rounds: int, out: str, rows: int = 4096) -> None:
+    """``--config tcn``: device time of every conv1d launch, the seq_pool and the dense head of the
+    typical abuse TCN (4 residual blocks x 64 channels, k = 3, dilations 1 2 4 8, T = 100, 16 inputs)
+    at ``rows`` rows, dense input; the whole model (runner.TcnModel.run); and, in the same interleaved
+    rounds, the 2 x 256 GRU of cfg5 (runner.GruModel.run, the K4 launch its engine_only path issues:
+    fp32 plan = split kernels, and bf16)."""
+    import torch
+    from igaming_platform_amd.engine.runner import sequence_model
+    from igaming_platform_amd.models.plan import compile_onnx, to_device
+    from igaming_platform_amd.native import hipk, native
+    from igaming_platform_amd.onnx import builders
+    from igaming_platform_amd.ops import kernels as K
+    dev = torch.device("cuda", 0)
+    T = 100
+    load = lambda m: native().OnnxModel.from_bytes(m.SerializeToString())
+    plan = to_device(compile_onnx(load(builders.tcn(channels=(64,) * 4, dilations=(1, 2, 4, 8)))), dev)
+    tm = sequence_model(plan.steps, dev, True, rows)
+    X = torch.from_numpy(np.random.default_rng(0).standard_normal((T, rows, 16)).astype(np.float32)).to(dev)
+    y = torch.zeros(rows, device=dev)
+    ops, flop = {}, 0
+    steps, p = tm.steps, tm.n_conv
+    for i, s in enumerate(steps[:p]):
+        src = s.src if s.src is not None else i - 1
+        kw = dict(X=X) if src < 0 else dict(A=tm.bufs[tm.buf_of[src]])
+        res = None if s.res is None else tm.bufs[tm.buf_of[s.res]]
+        ops[f"conv1d#{i}({s.c_in}->{s.c_out},k={s.k},d={s.dil})"] = (
+            lambda s=s, Y=tm.bufs[tm.buf_of[i]], kw=kw, res=res: K.conv1d(s, rows, T, Y, res=res, **kw))
+        flop += 2 * s.c_in * s.c_out * s.k * T
+    ops["seq_pool(last,64)"] = lambda: K.seq_pool("last", tm.bufs[tm.buf_of[p - 1]], tm.pooled, rows, T, 64)
+    ops["seq_pool(mean,64)"] = lambda: K.seq_pool("mean", tm.bufs[tm.buf_of[p - 1]], tm.pooled, rows, T, 64)
+    h = steps[-1]
+    ops["dense_head(64->1)"] = lambda: K.dense(tm.pooled, h.w, h.b, y.view(-1, 1), rows, 1, h.k, act=h.act)
+    ops["tcn_model"] = lambda: tm.run(rows, T, y, X=X)
+    for prec in ("fp32", "bf16"):
+        gp = to_device(compile_onnx(load(builders.gru(seq=T, in_dim=16, hidden=256, layers=2))), dev, prec)
+        gm = sequence_model(gp.steps, dev, prec != "bf16", rows)
+        ops[f"gru_2x256_model({prec})"] = lambda gm=gm: gm.run(rows, T, y, X=X)
+    times = {k: [] for k in ops}
+    for _ in range(rounds):
+        for k, f in ops.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            hipk().stall(torch.cuda.current_stream().cuda_stream, 300.0)  # device time only, as in main()
+            e0.record()
+            f()
+            e1.record()
+            e1.synchronize()
+            times[k].append(e0.elapsed_time(e1) * 1e3)
+    res = {k: dict(median_us=float(np.median(v[min(5, len(v) - 1):])), min_us=float(np.min(v[min(5, len(v) - 1):])))
+           for k, v in times.items()}
+    for k, v in res.items():
+        print(f"{k:34s} median {v['median_us']:9.1f} us   min {v['min_us']:9.1f} us")
+    t_tcn = res["tcn_model"]["median_us"]
+    summary = dict(rows=rows, T=T, mflop_per_row=flop / 1e6, tcn_rows_per_s=rows / t_tcn * 1e6,
+                   tcn_tflops=flop * rows / t_tcn / 1e6,
+                   gru_rows_per_s={p_: rows / res[f"gru_2x256_model({p_})"]["median_us"] * 1e6 for p_ in ("fp32", "bf16")})
+    print(json.dumps(summary))
+    if out:
+        with open(out, "w") as f:
+            json.dump(dict(config="tcn", kernels=res, summary=summary), f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", default="cfg3", help="a bench config, or rowops (the row-op kernels alone)")
+    ap.add_argument("--config", default="cfg3", help="a bench config, rowops (the row-op kernels alone) or tcn")
     ap.add_argument("--batch", type=int, default=0)
     ap.add_argument("--accounts", type=int, default=1 << 20)
     ap.add_argument("--rounds", type=int, default=50)
@@ -67,6 +130,8 @@ def main():
     a = ap.parse_args()
     if a.config == "rowops":
         return rowops(a.rounds, a.out)
+    if a.config == "tcn":
+        return tcn(a.rounds, a.out, a.batch or 4096)
     import torch
     from igaming_platform_amd.ops import kernels as K
     from igaming_platform_amd.utils import benchkit
